@@ -10,8 +10,8 @@ frames [32,4,800,1333] ~ N(0,1) (clip c: seed 42 + c), no padding, every frame g
 module's own initialisation under seed 42 (no checkpoints exist offline).  Every clip is sharded in contiguous
 blocks of 32/N frames over the N ranks (4 frames per GPU at N = 8), one rank per GPU, and the per-frame reference
 query sets are exchanged with one RCCL all-gather per step.  A step serves ONE clip (BASELINE.json configs[4]: one
-32-frame clip sharded 32/N frames per GPU - strong scaling: `value` = 32 * K / time whatever N is).  For N > 1 the
-line also carries `clip_stream_throughput`, measured after the timed region: N clips per step, every rank runs its
+32-frame clip sharded 32/N frames per GPU - strong scaling: `value` = 32 * K / time whatever N is).  For N > 1, --full
+adds `clip_stream_throughput`, measured after the timed region: N clips per step, every rank runs its
 32/N frames of each of them, i.e. 32 frames per rank and step whatever N is (the throughput mode of a stream of clips,
 weak scaling; --clips-per-step 0 makes it the timed mode).
 Inputs are resident in HBM before the timed region.  Compute type fp32 throughout.
@@ -23,7 +23,11 @@ Every MSDeformAttn's sampling_offsets.weight (zero at initialisation, so that al
 pattern) gets a fixed seeded perturbation N(0, 0.13^2): offsets then vary by ~2-3 pixels from query to query, the
 access pattern of a trained checkpoint, on the GPU model and the CPU baseline alike.
 
-The JSON line also carries
+A plain run sets up, warms up, times the K steps and prints the headline line (`value` frames/s, `ms_per_step`,
+`ms_per_step_p50`, `config`, `e2e`).  --dump-outputs DIR writes what the last timed step returned to its caller as
+DIR/<name>.npy (float32; integer picks as float64), so that two builds can be compared output for output.
+
+With --full the line also carries
   roofline     the kernel family with the largest share of GPU time in the timed steps - the fp32 MFMA GEMM
                (csrc/gemm_f32.hip: every 1x1 convolution and Linear): sum of 2*M*N*K flops over its launches /
                sum of their durations, against the dense fp32 matrix peak 157.3 TFLOP/s (MI355X_MICROARCH.md).
@@ -45,6 +49,8 @@ The JSON line also carries
                four ranks in five lie outside it: the oracle as checker at 800x1333).
   literal_mode (N=1 only) SURVEY.md 8d's secondary figure: the detector's own forward over the 32 frames -> ONE output (frame 0
                current), timed with the reference's protocol (benchmark.py:31-43: a device synchronize around every forward).
+  clip_stream_throughput  (N > 1, one clip per step) the throughput mode described above.
+and with or without it
   e2e          frames/s x the per-frame algorithmic work of config E (tools/algorithmic_work.py) against the chip's peaks:
                `fp32_mfma_frac` counts the 3x3 stride-1 convolutions in DIRECT-form flops (what the reference computes),
                `fp32_mfma_frac_executed` in the flops the Winograd kernel executes (1/2.25 of them).
@@ -175,6 +181,33 @@ def cpu_baseline(height, width, threads, frames=32, warm_frames=2, passes=3):
     return line
 
 
+DUMP_BUDGET = 64 << 20          # bytes --dump-outputs may write in all
+
+
+def dump_outputs(out, directory, prefix="", budget=DUMP_BUDGET):
+    """--dump-outputs: every tensor of ``out`` (the dictionary a caller of ClipRunner receives; a list entry becomes
+    <name>_<i>) as ``directory/<prefix><name>.npy`` - floating outputs in float32, integer ones (the temporal picks) in
+    float64, which holds them exactly.  Should the arrays exceed ``budget`` bytes, an array gets its share of the budget as
+    a fixed seeded sample of its flattened elements (sorted indices), the same elements in every run."""
+    import numpy as np
+    arrays = {}
+    for k, v in out.items():
+        for i, t in enumerate(v) if isinstance(v, (list, tuple)) else ((None, v),):
+            if torch.is_tensor(t):
+                t = t.detach().cpu()
+                arrays[k if i is None else f"{k}_{i}"] = t.numpy().astype(np.float32 if t.is_floating_point() else np.float64)
+    total = sum(x.nbytes for x in arrays.values())
+    room = budget - 4096 * len(arrays)                  # (room for the .npy headers)
+    os.makedirs(directory, exist_ok=True)
+    for name, x in arrays.items():
+        if total > room:
+            keep = max(1, room * x.nbytes // total // x.itemsize)
+            if keep < x.size:
+                idx = np.sort(np.random.default_rng(0).choice(x.size, keep, replace=False))
+                x = x.reshape(-1)[idx]
+        np.save(os.path.join(directory, f"{prefix}{name}.npy"), x)
+
+
 def launch_ranks(n):
     """``python bench.py --gpus N`` without a launcher: start the N ranks as fresh child processes (one per GPU) through
     torch.distributed.run with the arguments of this call, as the reference's own launcher forks its ranks
@@ -208,8 +241,15 @@ def main():
     ap.add_argument("--micro-batch", type=int, default=32,
                     help="frames per pass through the spatial stage (capped at the frames of the rank); larger "
                          "is faster up to the whole block: 8 -> 143.3, 16 -> 131.6, 32 -> 127.3 ms per 32-frame clip")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-literal", action="store_true", help="skip the secondary literal-mode figure (one output per clip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the figures beside the headline: roofline / roofline_kernels (kernels stamp their own events "
+                         "in the timed region, plus one extra single-stream step), clip_stream_throughput (N > 1), "
+                         "literal_mode and cpu_baseline (N = 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32 / float64, at most 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-literal", action="store_true",
+                    help="with --full: skip the secondary literal-mode figure (one output per clip)")
     ap.add_argument("--cpu-threads", type=int, default=16)
     ap.add_argument("--overlap", type=int, default=1,
                     help="two-stream schedule inside a rank: backbones of micro-batch i+1 beside the transformer "
@@ -289,12 +329,14 @@ def main():
     # RCCL with one rank (tests/test_clip_shard_gpu.py::test_rccl_call_path_with_one_rank) and with two ranks over gloo
     pipelined = n_micro == 1 and a.pipeline >= 1
     dones = []                                                      # completion events of the pipelined steps (HIP events)
+    last = {}                                                       # the outputs of the latest step (--dump-outputs)
 
     def step():
         if pipelined:
-            dones.append(runner.submit(mine, clips=clips)[1])
+            last["out"], done = runner.submit(mine, clips=clips)
+            dones.append(done)
         else:
-            runner(mine, clips=clips)
+            last["out"] = runner(mine, clips=clips)
 
     def barrier():
         if world > 1:
@@ -309,7 +351,8 @@ def main():
     for _ in range(a.warmup):
         step()
     barrier()
-    ops.profile_start()                                            # kernels stamp their own begin/end events
+    if a.full:
+        ops.profile_start()                                        # kernels stamp their own begin/end events
     # step marks without a host sync: with the clip pipeline the completion event of every step (recorded by submit on the
     # lane's tail stream, where the step's last kernel runs; the first interval starts at the last warm-up step's completion),
     # else events on the current stream
@@ -324,14 +367,16 @@ def main():
             marks[i + 1].record(torch.cuda.current_stream(device))
     barrier()
     dt = time.perf_counter() - t0
-    launches = ops.profile_stop()
+    launches = ops.profile_stop() if a.full else []
+    if a.dump_outputs:
+        dump_outputs(last["out"], a.dump_outputs, "" if rank == 0 else f"rank{rank}_", DUMP_BUDGET // world)
     stride = 1
     if pipelined:       # consecutive completions on ONE lane (one stream: ordered) are `lanes` steps apart
         stride = lanes
         marks = dones[max(first_timed - lanes, 0):]
     step_ms = sorted(marks[i].elapsed_time(marks[i + stride]) / stride for i in range(len(marks) - stride)) or [dt / a.steps * 1e3]
     timed_region_launches = None
-    if overlapped or pipelined:
+    if a.full and (overlapped or pipelined):
         # In the timed region the MSDA kernel shares the CUs with the other stream's convolutions, so
         # its stamped duration there is not the kernel's own.  The roofline figures come from one extra
         # single-stream step (same inputs, same kernels) after the timed region; both are reported.
@@ -348,7 +393,7 @@ def main():
     # beside the headline (one clip in flight), the throughput mode of a stream of clips: N clips per step, every rank runs
     # its T/N frames of each of them (T frames per step and rank whatever N is; one all-gather per step all the same)
     dt_stream = None
-    if world > 1 and clips == 1:
+    if a.full and world > 1 and clips == 1:
         block = [mine]
         for c in range(1, world):
             clip = torch.randn(a.frames, 4, a.height, a.width, generator=torch.Generator().manual_seed(42 + c))
@@ -465,24 +510,25 @@ def main():
                                       f"1 all-gather of the reference query sets per step",
                        "two_stream_overlap": overlapped, "clip_pipeline": pipelined, "pipeline_lanes": lanes if pipelined else 0, "hip_hw_queues": hw_queues,
                        "hip_graphs": use_graph and pipelined and bool(runner._graph_slots) and all(v is not False for v in runner._graph_slots.values())},
-            "roofline": roof,
-            "roofline_kernels": kernels,
-            "e2e": {"hbm_frac": round(fps / world * BYTES_PER_FRAME / HBM_PEAK, 4),
-                    "fp32_mfma_frac": round(fps / world * FLOPS_PER_FRAME / FP32_MFMA_PEAK, 4),
-                    "fp32_mfma_frac_executed": round(fps / world * FLOPS_EXECUTED_PER_FRAME / FP32_MFMA_PEAK, 4),
-                    "flops_per_frame_executed": FLOPS_EXECUTED_PER_FRAME,
-                    "bytes_per_frame": BYTES_PER_FRAME, "flops_per_frame": FLOPS_PER_FRAME,
-                    "source": "tools/algorithmic_work.py (config E, all-current mode)", "baseline_md": BASELINE_MD_PER_FRAME},
         }
+        if a.full:
+            line["roofline"] = roof
+            line["roofline_kernels"] = kernels
+        line["e2e"] = {"hbm_frac": round(fps / world * BYTES_PER_FRAME / HBM_PEAK, 4),
+                       "fp32_mfma_frac": round(fps / world * FLOPS_PER_FRAME / FP32_MFMA_PEAK, 4),
+                       "fp32_mfma_frac_executed": round(fps / world * FLOPS_EXECUTED_PER_FRAME / FP32_MFMA_PEAK, 4),
+                       "flops_per_frame_executed": FLOPS_EXECUTED_PER_FRAME,
+                       "bytes_per_frame": BYTES_PER_FRAME, "flops_per_frame": FLOPS_PER_FRAME,
+                       "source": "tools/algorithmic_work.py (config E, all-current mode)", "baseline_md": BASELINE_MD_PER_FRAME}
         if dt_stream is not None:
             line["clip_stream_throughput"] = {
                 "value": round(world * a.frames * a.steps / dt_stream, 3), "unit": "frames/s", "ms_per_step": round(dt_stream / a.steps * 1e3, 3),
                 "clips_per_step": world, "frames_per_gpu": world * per_rank, "scaling": "weak",
                 "note": "same run, after the timed region: N clips per step, every rank runs its T/N frames of each (throughput mode of a "
                         "stream of clips); NOT the headline - BASELINE.json's configuration is one clip sharded over the GPUs"}
-        if world == 1 and clips == 1 and not a.no_literal:
+        if a.full and world == 1 and clips == 1 and not a.no_literal:
             line["literal_mode"] = literal_mode(model, mine)
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(a.height, a.width, min(a.cpu_threads, os.cpu_count() or 1))
         print(json.dumps(line), flush=True)
     if world > 1:

@@ -3,7 +3,7 @@
 ``run_cases(ns)`` builds every block on the hot path from the module namespace ``ns``, fills
 its parameters by state_dict name (tests/_param_fill.py), feeds seeded inputs and returns the
 outputs.  tools/gen_golden_models.py calls it with the REFERENCE's modules (build container
-only) and stores the outputs in tests/golden/models.npz; tests/test_models_golden.py calls it
+only) and stores the outputs in tests/golden/models.part*.npz; tests/test_models_golden.py calls it
 with this repository's modules and compares.  Because one recipe drives both sides, the
 fixtures pin constructor signatures, call signatures and state_dict keys as well as numerics.
 

@@ -211,7 +211,8 @@ def test_bench_py_two_ranks_gloo_rehearsal(tmp_path, clips_per_step, pipeline, l
         cmd += ["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                 "--master-port", str(port)]
     cmd += [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--frames", "4",
-           "--height", "128", "--width", "160", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--pipeline", str(pipeline)]
+           "--height", "128", "--width", "160", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline",
+           "--pipeline", str(pipeline)]
     if clips_per_step is not None:
         cmd += ["--clips-per-step", str(clips_per_step)]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")

@@ -20,10 +20,10 @@ cover at least 80 % of the ranks outside the 2e-5 tie margin and report how many
 """
 import os
 
-import numpy as np
 import pytest
 import torch
 
+from tests import _golden
 from tests._cases_detector import compare_indices
 
 pytestmark = pytest.mark.gpu
@@ -137,7 +137,7 @@ def test_config_a_sample_image_through_the_whole_caller(golden_dir):
     from models.preprocess import RGB_MEAN, RGB_STD
     from oracle import preprocess_oracle as po
     from util.misc import NestedTensor
-    px = np.load(os.path.join(golden_dir, "oid_sample.npz"))["rgb"]
+    px = _golden.load(golden_dir, "oid_sample")["rgb"]
     assert px.shape == (1024, 773, 3)
     keep_prob = 0.5
     gm, post = _make(lambda d: single_args("Baseline", device=d), "cuda")

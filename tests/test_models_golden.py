@@ -11,6 +11,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests import _golden
+
 
 def my_namespace():
     import models.deformable_transformer_multi as tm
@@ -43,7 +45,7 @@ def cpu_roi(oracle, monkeypatch):
 
 @pytest.fixture(scope="module")
 def golden(golden_dir):
-    return np.load(os.path.join(golden_dir, "models.npz"))
+    return _golden.load(golden_dir, "models")
 
 
 def test_every_block_matches_the_reference(golden, cpu_msda, cpu_roi):

@@ -1,19 +1,19 @@
 """GPU parity of the whole host-side stack on the HIP kernels: every block of tests/_cases.py run
-on cuda:0 (fused MSDA front end, HIP RoIAlign) against the reference's outputs (models.npz), the
+on cuda:0 (fused MSDA front end, HIP RoIAlign) against the reference's outputs (models.part*.npz), the
 detector through build_model against the same detector on CPU with the oracle operators, and the
 box indices of the post-processor."""
-import os
 
-import numpy as np
 import pytest
 import torch
+
+from tests import _golden
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
 def golden(golden_dir):
-    return np.load(os.path.join(golden_dir, "models.npz"))
+    return _golden.load(golden_dir, "models")
 
 
 def test_every_block_matches_the_reference_on_gpu(golden):

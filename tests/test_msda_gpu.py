@@ -3,11 +3,11 @@
 Tolerances: fp32 attention outputs within 1e-3 absolute (BASELINE.json north_star); we assert a
 tighter 2e-5 * scale here.  fp64 within the reference's own allclose defaults (test.py:39).
 """
-import os
 
-import numpy as np
 import pytest
 import torch
+
+from tests import _golden
 
 pytestmark = pytest.mark.gpu
 
@@ -25,7 +25,7 @@ def msda():
 
 @pytest.fixture(scope="module")
 def z(golden_dir):
-    return np.load(os.path.join(golden_dir, "msda_op.npz"))
+    return _golden.load(golden_dir, "msda_op")
 
 
 def _t(z, case, key, dev="cuda"):

@@ -1,9 +1,9 @@
 """CPU: the C oracle against the vectors generated from the reference (tools/gen_golden_op.py)."""
-import os
 
-import numpy as np
 import pytest
 import torch
+
+from tests import _golden
 
 CASES_F32 = ["testpy_f32", "enc_l1", "dec_l1", "ms_l4", "border", "flatquirk"]
 CASES_F64 = ["testpy_f64", "odd", "enc_l1_f64"]
@@ -12,7 +12,7 @@ GRAD_CASES = ["ms_l4", "border", "odd", "enc_l1_f64"]
 
 @pytest.fixture(scope="module")
 def z(golden_dir):
-    return np.load(os.path.join(golden_dir, "msda_op.npz"))
+    return _golden.load(golden_dir, "msda_op")
 
 
 def _t(z, case, key):

@@ -3,7 +3,7 @@
 Build container only (imports /root/reference through tools/ref_import.py):
     python tools/gen_golden_models.py
 Runs the shared recipes of tests/_cases.py against the reference's modules and writes their
-outputs to tests/golden/models.npz.  Neither weights
+outputs to tests/golden/models.part*.npz.  Neither weights
 nor inputs are stored: both are regenerated from seeds / state_dict names on the test side.
 
 The MSDA operator inside the reference modules is the reference's ms_deform_attn_core_pytorch
@@ -40,6 +40,7 @@ from models.position_encoding import PositionEmbeddingSine  # noqa: E402
 from models.sparse_roi_head.head import RCNNHead  # noqa: E402
 from util.misc import NestedTensor, inverse_sigmoid  # noqa: E402
 
+from tests import _golden  # noqa: E402
 from tests._cases import run_cases, run_train_cases  # noqa: E402
 
 ns = SimpleNamespace(MSDeformAttn=MSDeformAttn, ts=ts, tpp=tpp, tm=tm, RCNNHead=RCNNHead, dfb=dfb, dcf=dcf,
@@ -47,9 +48,8 @@ ns = SimpleNamespace(MSDeformAttn=MSDeformAttn, ts=ts, tpp=tpp, tm=tm, RCNNHead=
                      inverse_sigmoid=inverse_sigmoid)
 torch.set_grad_enabled(False)
 blobs = {k: v.numpy() for k, v in run_cases(ns).items()}
-OUT = os.path.join(ROOT, "tests", "golden", "models.npz")
-np.savez_compressed(OUT, **blobs)
-print("wrote", OUT, f"{os.path.getsize(OUT)/1e6:.2f} MB", len(blobs), "arrays")
+_golden.save(os.path.join(ROOT, "tests", "golden"), "models", blobs)      # in parts of < 1 MiB
+print("wrote tests/golden/models.part*.npz", len(blobs), "arrays")
 
 # the blocks in TRAIN mode under a fixed seed (sub-layer Dropouts active): tests/golden/train_mode.npz
 blobs = {k: v.numpy() for k, v in run_train_cases(ns).items()}

@@ -2,7 +2,7 @@
 
 Run in the build container only (needs /root/reference):
     python tools/gen_golden_op.py
-Writes tests/golden/msda_op.npz.  Expected outputs come from the reference's
+Writes tests/golden/msda_op.part*.npz.  Expected outputs come from the reference's
 ms_deform_attn_core_pytorch (models/ops/functions/ms_deform_attn_func.py:41-61);
 gradients come from autograd through that same function in float64, which is
 what models/ops/test.py:63-78 checks the CUDA backward against (gradcheck).
@@ -20,7 +20,6 @@ Cases
 import os
 import sys
 
-import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
@@ -28,7 +27,7 @@ import ref_import  # noqa: E402
 
 fmod = ref_import.install()
 core = fmod.ms_deform_attn_core_pytorch
-OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden", "msda_op.npz")
+GOLDEN = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
 
 
 def lsi_of(shapes):
@@ -95,8 +94,10 @@ def main():
         out = fmod.FlatShim.apply(value, shapes, lsi_of(shapes), loc, aw, 64)
     put("flatquirk", dict(value=value, shapes=shapes, lsi=lsi_of(shapes), loc=loc, aw=aw, out=out))
 
-    np.savez_compressed(OUT, **blobs)
-    print("wrote", os.path.normpath(OUT), f"{os.path.getsize(OUT)/1e3:.0f} kB", len(blobs), "arrays")
+    sys.path.insert(0, os.path.dirname(GOLDEN))
+    import _golden
+    _golden.save(GOLDEN, "msda_op", blobs)                          # in parts of < 1 MiB
+    print("wrote tests/golden/msda_op.part*.npz", len(blobs), "arrays")
 
 
 if __name__ == "__main__":

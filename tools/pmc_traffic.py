@@ -40,6 +40,6 @@ for key in dict.fromkeys(k for k, _ in FAM):
     doc[key] = {"launches_per_step": n, "fetch_bytes_per_step": rd * 1e6, "write_bytes_per_step": wr * 1e6}
 if len(sys.argv) > 4:
     with open(sys.argv[4], "w") as fh:
-        json.dump({"steps_profiled": steps, "frames_per_step": 32, "workload": "bench.py --no-cpu-baseline --pipeline 0 --steps 2 --warmup 1",
+        json.dump({"steps_profiled": steps, "frames_per_step": 32, "workload": "bench.py --full --no-cpu-baseline --pipeline 0 --steps 2 --warmup 1",
                    "note": "fabric side of L2 (HBM + Infinity Cache): 2 x FETCH_SIZE (gfx950 correction) + WRITE_SIZE, separate PMC passes",
                    "families": doc}, fh, indent=1, sort_keys=True)
