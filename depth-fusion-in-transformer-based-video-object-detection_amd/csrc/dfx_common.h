@@ -69,6 +69,7 @@ struct Tuning {
     bool level_not_persistent = false;  // DFX_LEVEL_NOT_PERSISTENT
     bool level_variant_set = false;  // DFX_LEVEL_VARIANT given
     int level_variant = 0;           // DFX_LEVEL_VARIANT: kernel variant of msda_level.hip (A/B)
+    bool msda_half_narrow = false;   // DFX_MSDA_HALF_NARROW: 8-byte (8 lanes per head) gather of msda_half.hip at L = 1 too (A/B)
     void read()
     {
         *this = Tuning();
@@ -87,6 +88,7 @@ struct Tuning {
         level_not_persistent = flag("DFX_LEVEL_NOT_PERSISTENT");
         level_variant_set = flag("DFX_LEVEL_VARIANT");
         level_variant = num("DFX_LEVEL_VARIANT", 0);
+        msda_half_narrow = flag("DFX_MSDA_HALF_NARROW");
     }
 };
 inline Tuning &tuning_slot()

@@ -19,7 +19,9 @@ struct Tap {
 
 // Geometry of one sample; follows /root/reference/models/ops/src/cuda/ms_deform_im2col_cuda.cuh
 // :281-291 (pixel coordinates, skip rule) and :33-84 (corner validity, bilinear weights).
-// `head_bytes` = m * 128, `level_row` = level_start_index[l] (rows of 1 KiB = 8 heads x 32 fp32).
+// `head_bytes` = m * ROW_BYTES / 8, `level_row` = level_start_index[l] (token rows of ROW_BYTES:
+// 1 KiB = 8 heads x 32 fp32, 512 B = 8 heads x 32 bf16 / fp16).
+template <unsigned ROW_BYTES = 1024u>
 __device__ __forceinline__ Tap make_tap(float lx, float ly, float a, int H, int W, int level_row,
                                         int head_bytes)
 {
@@ -47,11 +49,50 @@ __device__ __forceinline__ Tap make_tap(float lx, float ly, float a, int H, int 
     const int y0 = max(min(h0, H - 1), 0), y1 = max(min(h1, H - 1), 0);
     const int x0 = max(min(w0, W - 1), 0), x1 = max(min(w1, W - 1), 0);
     const int r0 = level_row + y0 * W, r1 = level_row + y1 * W;
-    t.off.x = (unsigned)(r0 + x0) * 1024u + (unsigned)head_bytes;
-    t.off.y = (unsigned)(r0 + x1) * 1024u + (unsigned)head_bytes;
-    t.off.z = (unsigned)(r1 + x0) * 1024u + (unsigned)head_bytes;
-    t.off.w = (unsigned)(r1 + x1) * 1024u + (unsigned)head_bytes;
+    t.off.x = (unsigned)(r0 + x0) * ROW_BYTES + (unsigned)head_bytes;
+    t.off.y = (unsigned)(r0 + x1) * ROW_BYTES + (unsigned)head_bytes;
+    t.off.z = (unsigned)(r1 + x0) * ROW_BYTES + (unsigned)head_bytes;
+    t.off.w = (unsigned)(r1 + x1) * ROW_BYTES + (unsigned)head_bytes;
     return t;
+}
+
+// Phase A of the unfused wave-per-query forward (M = 8 heads, P = 4 points, LT levels): lane =
+// one (query, level, point, head) sample of the QW queries q0 .. q0+QW-1; it reads its (x, y)
+// pair and attention weight once and writes its tap to LDS slot ((qq*LT + l)*4 + p)*8 + head.
+// Queries at or past NQ get zero taps (offset 0, weight 0).  (msda_fwd_taps keeps the fp32 form of
+// this loop inline: routing it through here changes that kernel's instruction schedule.)
+template <int LT>
+struct LevelDims {
+    int H[LT], W[LT], R[LT];     // (H_l, W_l, level_start_index[l]) of every level
+};
+
+template <int LT, int QW, unsigned ROW_BYTES>
+__device__ __forceinline__ void write_taps(const float *__restrict__ loc, const float *__restrict__ aw, int q0,
+                                           int NQ, int lane, const LevelDims<LT> lv, uint4 *toff, float4 *tw)
+{
+    constexpr int TAPS = QW * LT * 32;    // taps per wave per iteration (multiple of 64)
+#pragma unroll
+    for (int c = 0; c < TAPS / 64; ++c) {
+        const int s = c * 64 + lane;                 // slot = ((qq*LT + l)*4 + p)*8 + head
+        const int hm = s & 7, p = (s >> 3) & 3, ql = s >> 5;
+        const int l = (LT == 1) ? 0 : ql % LT, qq = (LT == 1) ? ql : ql / LT;
+        const int qi = q0 + qq;
+        Tap t;
+        if (qi < NQ) {
+            const long e = (((long)qi * 8 + hm) * LT + l) * 4 + p;
+            const float2 xy = *reinterpret_cast<const float2 *>(loc + e * 2);
+            int H = lv.H[0], W = lv.W[0], R = lv.R[0];
+#pragma unroll
+            for (int k = 1; k < LT; ++k)
+                if (l == k) { H = lv.H[k]; W = lv.W[k]; R = lv.R[k]; }
+            t = make_tap<ROW_BYTES>(xy.x, xy.y, aw[e], H, W, R, hm * (int)(ROW_BYTES / 8));
+        } else {
+            t.off = make_uint4(0u, 0u, 0u, 0u);
+            t.w = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+        toff[s] = t.off;
+        tw[s] = t.w;
+    }
 }
 
 __device__ __forceinline__ void fma4(float4 &acc, float w, const float4 &v)

@@ -17,6 +17,11 @@ SIGNATURES = {
     "dfx_msda_forward_f64": [_p] * 5 + _DIMS + [_p, _p],
     "dfx_msda_backward_f32": [_p] * 6 + _DIMS + [_p, _p, _p, _p],
     "dfx_msda_backward_f64": [_p] * 6 + _DIMS + [_p, _p, _p, _p],
+    # 2-byte value / grad_out / out, fp32 loc / aw / gradients (csrc/msda_half.hip)
+    "dfx_msda_forward_bf16": [_p] * 5 + _DIMS + [_p, _p],
+    "dfx_msda_forward_f16": [_p] * 5 + _DIMS + [_p, _p],
+    "dfx_msda_backward_bf16": [_p] * 6 + _DIMS + [_p, _p, _p, _p],
+    "dfx_msda_backward_f16": [_p] * 6 + _DIMS + [_p, _p, _p, _p],
     "dfx_msda_fused_forward_f32": [_p, _p, _p, _p, _i, _i, _p, _l, _p, _l] + _DIMS + [_p, _p],
     "dfx_profile_enable": [_i],
     "dfx_tuning_reload": [],

@@ -12,6 +12,8 @@ import torch
 from . import _lib
 
 _SUFFIX = {torch.float32: "f32", torch.float64: "f64"}
+# 2-byte value maps (mixed precision, csrc/msda_half.hip): sampling_loc and attn_weight stay fp32
+_HALF_SUFFIX = {torch.bfloat16: "bf16", torch.float16: "f16"}
 ACT = {None: 0, "none": 0, "relu": 1, "gelu": 2}
 
 # Single-level attention with many queries (encoder, depth fusion) runs on the level-in-LDS kernel
@@ -109,21 +111,33 @@ def _on(dev):
     return torch.cuda.device(dev)
 
 
+def _operand_dtypes(what, value, sampling_loc, attn_weight):
+    """The operator's dtype contract -> library suffix: fp32 / fp64 with locations and weights of the same dtype, or a
+    bf16 / fp16 value with fp32 locations and weights (what MSDeformAttn produces under torch.autocast)."""
+    if value.dtype in _HALF_SUFFIX:
+        if sampling_loc.dtype != torch.float32 or attn_weight.dtype != torch.float32:
+            raise RuntimeError(f"{what}: a {value.dtype} value needs fp32 (torch.float32) sampling_loc and attn_weight, "
+                               f"got {sampling_loc.dtype} and {attn_weight.dtype}")
+        return _HALF_SUFFIX[value.dtype]
+    _require(value.dtype in _SUFFIX, f"{what} not implemented for {value.dtype}")
+    _require(sampling_loc.dtype == value.dtype and attn_weight.dtype == value.dtype,
+             "value, sampling_loc and attn_weight must share one dtype")
+    return _SUFFIX[value.dtype]
+
+
 def msda_forward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, im2col_step=64):
     lib = _lib.load()
     _check_inputs([("value", value), ("spatial_shapes", spatial_shapes),
                    ("level_start_index", level_start_index), ("sampling_loc", sampling_loc),
                    ("attn_weight", attn_weight)])
-    _require(value.dtype in _SUFFIX, f"ms_deform_attn_forward not implemented for {value.dtype}")
-    _require(sampling_loc.dtype == value.dtype and attn_weight.dtype == value.dtype,
-             "value, sampling_loc and attn_weight must share one dtype")
+    suffix = _operand_dtypes("ms_deform_attn_forward", value, sampling_loc, attn_weight)
     _require(spatial_shapes.dtype == torch.int64 and level_start_index.dtype == torch.int64,
              "spatial_shapes and level_start_index must be int64")
     N, S, M, D, L, Lq, P = _dims(value, spatial_shapes, sampling_loc, im2col_step)
     _require(sampling_loc.numel() >= N * Lq * M * L * P * 2 and attn_weight.numel() >= N * Lq * M * L * P,
              "sampling_loc / attn_weight smaller than N*Lq*M*L*P")
     out = torch.empty((N, Lq, M * D), dtype=value.dtype, device=value.device)
-    fn = getattr(lib, "dfx_msda_forward_" + _SUFFIX[value.dtype])
+    fn = getattr(lib, "dfx_msda_forward_" + suffix)
     with _on(value.device):
         rc = fn(value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(),
                 sampling_loc.data_ptr(), attn_weight.data_ptr(), N, S, M, D, L, Lq, P,
@@ -138,21 +152,24 @@ def msda_backward(value, spatial_shapes, level_start_index, sampling_loc, attn_w
     _check_inputs([("value", value), ("spatial_shapes", spatial_shapes),
                    ("level_start_index", level_start_index), ("sampling_loc", sampling_loc),
                    ("attn_weight", attn_weight), ("grad_output", grad_output)])
-    _require(value.dtype in _SUFFIX, f"ms_deform_attn_backward not implemented for {value.dtype}")
-    _require(sampling_loc.dtype == value.dtype and attn_weight.dtype == value.dtype
-             and grad_output.dtype == value.dtype, "all floating inputs must share one dtype")
+    suffix = _operand_dtypes("ms_deform_attn_backward", value, sampling_loc, attn_weight)
+    _require(grad_output.dtype == value.dtype, f"grad_output must have value's dtype {value.dtype}, got {grad_output.dtype}")
     N, S, M, D, L, Lq, P = _dims(value, spatial_shapes, sampling_loc, im2col_step)
     _require(grad_output.numel() == N * Lq * M * D, "grad_output has the wrong size")
-    grad_value = torch.zeros_like(value)
+    half = value.dtype in _HALF_SUFFIX
+    # a 2-byte value's gradient is accumulated in fp32 (atomics) and rounded once below
+    grad_value = torch.zeros(value.shape, dtype=torch.float32, device=value.device) if half else torch.zeros_like(value)
     grad_loc = torch.zeros_like(sampling_loc)
     grad_aw = torch.zeros_like(attn_weight)
-    fn = getattr(lib, "dfx_msda_backward_" + _SUFFIX[value.dtype])
+    fn = getattr(lib, "dfx_msda_backward_" + suffix)
     with _on(value.device):
         rc = fn(value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(),
                 sampling_loc.data_ptr(), attn_weight.data_ptr(), grad_output.data_ptr(),
                 N, S, M, D, L, Lq, P, grad_value.data_ptr(), grad_loc.data_ptr(), grad_aw.data_ptr(),
                 _stream(value.device))
     _lib.check(rc, "ms_deform_attn_backward")
+    if half:
+        grad_value = grad_value.to(value.dtype)
     return [grad_value, grad_loc, grad_aw]
 
 

@@ -102,6 +102,31 @@ int dfx_msda_backward_f64(const double *value, const int64_t *shapes, const int6
                           double *grad_value, double *grad_loc, double *grad_aw, void *stream);
 
 /*
+ * 2-byte value maps (mixed precision: what MSDeformAttn hands the operator under torch.autocast).
+ * value, grad_out and out are bf16 (the _bf16 pair) or IEEE fp16 (the _f16 pair), passed as raw
+ * 16-bit words; loc and aw are fp32 in every case.  The arithmetic is the fp32 operator's (corner
+ * weights, products and the sum over L*P samples in fp32), and each output element is rounded once
+ * to the value's type.  Backward accumulates into three zero-filled fp32 buffers: grad_value_f32 is
+ * laid out like value ([N,S,M,D] floats) and the caller rounds it to the value's type.
+ * Replaces the same reference lines as the fp32 pairs above (which dispatch fp32 / fp64 only,
+ * AT_DISPATCH_FLOATING_TYPES, ms_deform_attn_cuda.cu:64,136).
+ */
+int dfx_msda_forward_bf16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
+                          const float *loc, const float *aw, int N, int S, int M, int D, int L, int Lq, int P,
+                          uint16_t *out, void *stream);
+int dfx_msda_backward_bf16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
+                           const float *loc, const float *aw, const uint16_t *grad_out,
+                           int N, int S, int M, int D, int L, int Lq, int P,
+                           float *grad_value_f32, float *grad_loc, float *grad_aw, void *stream);
+int dfx_msda_forward_f16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
+                         const float *loc, const float *aw, int N, int S, int M, int D, int L, int Lq, int P,
+                         uint16_t *out, void *stream);
+int dfx_msda_backward_f16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
+                          const float *loc, const float *aw, const uint16_t *grad_out,
+                          int N, int S, int M, int D, int L, int Lq, int P,
+                          float *grad_value_f32, float *grad_loc, float *grad_aw, void *stream);
+
+/*
  * Fused front end + sampling (inference): what MSDeformAttn.forward does between
  * its Linear layers (/root/reference/models/ops/modules/ms_deform_attn.py:98-114):
  *   aw  = softmax over (L*P) of logits[b,q,m,:]

@@ -4,6 +4,15 @@ python tools/bench_msda.py [--frames 32] [--iters 200]
 Prints algorithmic GB/s per call (value + loc/aw + out bytes) for
   enc  : N=frames, Lq=S=4200, L=1      dec : N=frames, Lq=300, S=4200, L=1
   enc4 : N=frames/4, Lq=S=22223, L=4   unfused vs fused front end.
+
+python tools/bench_msda.py --dtype {f32,bf16,f16} [--repeats 5]
+The unfused operator (MultiScaleDeformableAttention.ms_deform_attn_forward / _backward) with a value map of that
+dtype and fp32 locations / weights, forward and backward, at enc L1, dec L1 and enc L4 (uniform locations).  Each
+timing is repeated --repeats times (median and range).  Forward GB/s counts e*N*S*M*D + 12*N*Lq*M*L*P + e*N*Lq*M*D
+bytes (e = 2 for bf16 / fp16, 4 for fp32); backward GB/s counts e*(N*S*M*D + N*Lq*M*D) + 24*N*Lq*M*L*P +
+4*N*S*M*D (value, grad_out, loc / aw and their gradients, the fp32 grad_value accumulator) per call, which
+also zero-fills the gradients (and rounds grad_value to the value's dtype).  For bf16 / fp16 the forward is also
+timed with DFX_MSDA_HALF_NARROW=1 (the 8-byte gather at every L; the default takes it for L > 1 only).
 """
 import argparse
 import os
@@ -31,11 +40,61 @@ def timeit(fn, iters):
     return a.elapsed_time(b) / iters * 1e-3
 
 
+def spread(fn, iters, repeats):
+    ts = sorted(timeit(fn, iters) for _ in range(repeats))
+    return ts[len(ts) // 2], ts[0], ts[-1]
+
+
+def dtype_table(a):
+    dt = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}[a.dtype]
+    e = 4 if dt == torch.float32 else 2
+    dev = "cuda"
+    M, D, P = 8, 32, 4
+    print(f"dtype {a.dtype}: value {dt}, loc / aw fp32; iters {a.iters}, repeats {a.repeats}; "
+          f"median [min, max] per call", flush=True)
+    for name, N, Lq, shp in (("enc_L1", a.frames, 4200, [(50, 84)]), ("dec_L1", a.frames, 300, [(50, 84)]),
+                             ("enc_L4", max(1, a.frames // 4), 22223, [(100, 167), (50, 84), (25, 42), (13, 21)])):
+        shapes = torch.as_tensor(shp, dtype=torch.long, device=dev)
+        lsi = torch.cat((shapes.new_zeros((1,)), shapes.prod(1).cumsum(0)[:-1]))
+        L, S = len(shp), int(shapes.prod(1).sum())
+        value = torch.randn(N, S, M, D, device=dev).to(dt)
+        loc = torch.rand(N, Lq, M, L, P, 2, device=dev)
+        aw = torch.softmax(torch.randn(N, Lq, M, L * P, device=dev), -1).view(N, Lq, M, L, P)
+        go = torch.randn(N, Lq, M * D, device=dev).to(dt)
+        fwd_bytes = e * N * S * M * D + 12 * N * Lq * M * L * P + e * N * Lq * M * D
+        bwd_bytes = e * (N * S * M * D + N * Lq * M * D) + 24 * N * Lq * M * L * P + 4 * N * S * M * D
+
+        def fmt(label, t, nbytes):
+            med, lo, hi = t
+            return f" | {label} {med*1e6:8.1f} us [{lo*1e6:.1f}, {hi*1e6:.1f}] {nbytes/med/1e9:7.1f} GB/s alg"
+
+        line = f"{name:7s} N={N:3d} Lq={Lq:6d} L={L} S={S:6d}"
+        line += fmt("fwd", spread(lambda: MSDA.ms_deform_attn_forward(value, shapes, lsi, loc, aw, 64),
+                                  a.iters, a.repeats), fwd_bytes)
+        if dt != torch.float32:
+            os.environ["DFX_MSDA_HALF_NARROW"] = "1"
+            ops.reload_tuning()
+            line += fmt("fwd narrow", spread(lambda: MSDA.ms_deform_attn_forward(value, shapes, lsi, loc, aw, 64),
+                                             a.iters, a.repeats), fwd_bytes)
+            del os.environ["DFX_MSDA_HALF_NARROW"]
+            ops.reload_tuning()
+        biters = max(1, a.iters // 4)
+        line += fmt("bwd", spread(lambda: MSDA.ms_deform_attn_backward(value, shapes, lsi, loc, aw, go, 64),
+                                  biters, a.repeats), bwd_bytes)
+        print(line, flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=32)
     ap.add_argument("--iters", type=int, default=200)
+    ap.add_argument("--dtype", choices=("f32", "bf16", "f16"), default=None,
+                    help="time the unfused operator forward + backward with a value map of this dtype")
+    ap.add_argument("--repeats", type=int, default=5)
     a = ap.parse_args()
+    if a.dtype is not None:
+        dtype_table(a)
+        return
     torch.manual_seed(42)
     dev = "cuda"
     M, D, P = 8, 32, 4
