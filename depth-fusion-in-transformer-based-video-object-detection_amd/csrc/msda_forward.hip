@@ -30,11 +30,40 @@
 // Roofline: HBM-bound gather.  Algorithmic bytes per call
 //   4 * (N*S*M*D  +  3*N*Lq*M*L*P  +  N*Lq*M*D)       (value + loc/aw + out, fp32)
 // = 10.21 MB per frame for the encoder geometry (S = Lq = 4200, L = 1).
+//
+// 2-byte value maps (bf16 / fp16, dfx_msda_{forward,backward}_{bf16,f16}): the mixed-precision form of
+// the operator - what MSDeformAttn hands the op under torch.autocast - value from a Linear (bf16 /
+// fp16), sampling locations and attention weights in fp32 (include/dfx_msda.h, dfx_msda_forward_bf16).
+// Only the value map, grad_output and the forward output are 2-byte; the arithmetic is the fp32 op's:
+// corner weights, products and the sum over L*P samples in fp32, one rounding per output element
+// (a plain conversion, v_cvt_pk_{bf16,f16}_f32).  Backward accumulates grad_value into an fp32
+// buffer with float atomics (a packed 2-byte atomic would round at every add).
+//
+//   forward, M = 8, D = 32, P = 4, L <= 4, 16-byte aligned value / out: msda_half_fwd_taps.  Phase A
+//            is msda_fwd_taps' (msda_tap.h, write_taps with 512-byte token rows); phase B gathers
+//            each corner as 2-byte channels, accumulates in fp32 registers and stores the output
+//            row in the value dtype.  Two gather widths, the same bits:
+//              wide    4 lanes x 16 B per head: 8 channels a lane, both queries of the wave in one pass
+//              narrow  8 lanes x  8 B per head: 4 channels a lane, one query per pass (the fp32 mapping)
+//            wide for L = 1 (bf16, 32 frames: enc 98 us against 130, dec 12.9 against 14.2), narrow for more
+//            levels (enc L4: 601 us against 621; wide holds 16 corner rows of 16 B per level in flight and
+//            needs 178-256 VGPRs at L >= 2).  DFX_MSDA_HALF_NARROW=1 takes narrow for every L (A/B).
+//   forward, anything else: msda_fwd_generic<bf16 / fp16>, one thread per output element, scalar 2-byte
+//            reads (odd D, any alignment).
+//   backward (msda_backward.hip), M = 8, D = 32, 16-byte aligned value / grad_out: msda_bwd_m8d32<bf16 /
+//            fp16> (8-byte corner and grad_out reads); anything else msda_bwd_generic<bf16 / fp16>.
+//
+// Algorithmic bytes of a 2-byte forward call: 2*N*S*M*D + 12*N*Lq*M*L*P + 2*N*Lq*M*D
+// (5.91 MB per encoder frame, S = Lq = 4200, L = 1; 10.21 MB in fp32).
 #include "dfx_common.h"
 #include "msda_tap.h"
 
 namespace {
 
+using dfx::Acc;
+using dfx::narrow4;
+using dfx::Pack;
+using dfx::widen4;
 using dfx::xcd_remap;
 
 struct Corner4 {
@@ -213,19 +242,154 @@ __global__ __launch_bounds__(256) void msda_fwd_taps(const float *__restrict__ v
 }
 
 // ---------------------------------------------------------------------------------------------
-// Generic path: any M, D, L, P; fp32 and fp64.  One thread per output element, channel fastest
-// (adjacent lanes read adjacent channels of the same value row), grid-stride.  Used by the
-// reference's tiny test fixture (M=D=2), odd head sizes and every fp64 call.
+// Forward fast path: M = 8, D = 32, P = 4, LT levels (1..4), 2-byte value / out, fp32 loc / aw.
+// Token rows are 512 bytes (8 heads x 64 B).  A 256-thread workgroup = 4 waves x 2 queries.
 // ---------------------------------------------------------------------------------------------
-template <typename T>
-__global__ __launch_bounds__(256) void msda_fwd_generic(const T *__restrict__ value,
+template <int LT, typename T, bool WIDE>
+__global__ __launch_bounds__(256) void msda_half_fwd_taps(const T *__restrict__ value,
+                                                          const int64_t *__restrict__ shapes,
+                                                          const int64_t *__restrict__ lsi,
+                                                          const float *__restrict__ loc,
+                                                          const float *__restrict__ aw, int NQ, int Lq,
+                                                          int S, int iters, T *__restrict__ out)
+{
+    constexpr int QW = 2;                 // queries per wave per iteration
+    constexpr int TAPS = QW * LT * 32;
+    __shared__ uint4 s_off[4][TAPS];
+    __shared__ float4 s_w[4][TAPS];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    uint4 *toff = s_off[wave];
+    float4 *tw = s_w[wave];
+    const int blk = xcd_remap(blockIdx.x, gridDim.x);
+    const unsigned slab = (unsigned)S * 512u;     // bytes of one batch element's value map
+
+    dfx::LevelDims<LT> lv;
+#pragma unroll
+    for (int l = 0; l < LT; ++l) {
+        lv.H[l] = (int)shapes[2 * l];
+        lv.W[l] = (int)shapes[2 * l + 1];
+        lv.R[l] = (int)lsi[l];
+    }
+
+    for (int it = 0; it < iters; ++it) {
+        const int q0 = ((blk * iters + it) * 4 + wave) * QW;   // first query of this wave (uniform)
+        if (q0 >= NQ) break;
+        // ---- phase A: one tap per lane ----
+        dfx::write_taps<LT, QW, 512u>(loc, aw, q0, NQ, lane, lv, toff, tw);
+        dfx::wave_lds_fence();
+        // ---- phase B: gather ----
+        const int b0 = q0 / Lq;
+        const char *vb = reinterpret_cast<const char *>(value) + (size_t)b0 * slab;
+        if (WIDE) {
+            // lane = (query qq = lane>>5, head m = (lane>>2)&7, channel octet cg = lane&3); the pair may
+            // straddle two batch elements, so the second one's slab goes into the lane's offset
+            // (< 2 * slab <= S * 1024 < 2^32: the launcher's bound).  A query past NQ has zero taps.
+            const int qq = lane >> 5, m = (lane >> 2) & 7;
+            const int qi = q0 + qq;
+            const int b = qi < NQ ? qi / Lq : b0;
+            const unsigned lane_b = (unsigned)(lane & 3) * 16u + (unsigned)(b - b0) * slab;
+            const uint4 *qo = toff + qq * LT * 32;
+            const float4 *qw = tw + qq * LT * 32;
+            float4 lo = make_float4(0.f, 0.f, 0.f, 0.f), hi = lo;
+#pragma unroll
+            for (int l = 0; l < LT; ++l) {
+                uint4 o[4];
+                float4 w[4];
+#pragma unroll
+                for (int p = 0; p < 4; ++p) {
+                    o[p] = qo[(l * 4 + p) * 8 + m];
+                    w[p] = qw[(l * 4 + p) * 8 + m];
+                }
+                Pack<T, 8> v[16];
+#pragma unroll
+                for (int p = 0; p < 4; ++p) {
+                    v[p * 4 + 0] = *reinterpret_cast<const Pack<T, 8> *>(vb + (o[p].x + lane_b));
+                    v[p * 4 + 1] = *reinterpret_cast<const Pack<T, 8> *>(vb + (o[p].y + lane_b));
+                    v[p * 4 + 2] = *reinterpret_cast<const Pack<T, 8> *>(vb + (o[p].z + lane_b));
+                    v[p * 4 + 3] = *reinterpret_cast<const Pack<T, 8> *>(vb + (o[p].w + lane_b));
+                }
+#pragma unroll
+                for (int p = 0; p < 4; ++p) {
+                    const float wk[4] = {w[p].x, w[p].y, w[p].z, w[p].w};
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const Pack<T, 8> &c = v[p * 4 + k];
+                        fma4(lo, wk[k], make_float4((float)c.v[0], (float)c.v[1], (float)c.v[2], (float)c.v[3]));
+                        fma4(hi, wk[k], make_float4((float)c.v[4], (float)c.v[5], (float)c.v[6], (float)c.v[7]));
+                    }
+                }
+            }
+            if (qi < NQ) {
+                const Pack<T, 4> a = narrow4<T>(lo), c = narrow4<T>(hi);
+                Pack<T, 8> r;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    r.v[k] = a.v[k];
+                    r.v[4 + k] = c.v[k];
+                }
+                *reinterpret_cast<Pack<T, 8> *>(out + (long)qi * 256 + (lane & 31) * 8) = r;
+            }
+        } else {
+            // lane = (head m = lane>>3, channel quad cg = lane&7), one query per pass
+            const int m = lane >> 3;
+            const unsigned lane_b = (unsigned)(lane & 7) * 8u;
+#pragma unroll
+            for (int qq = 0; qq < QW; ++qq) {
+                const int qi = q0 + qq;
+                if (qi < NQ) {
+                    const char *vq = reinterpret_cast<const char *>(value) + (size_t)(qi / Lq) * slab;
+                    const uint4 *qo = toff + qq * LT * 32;
+                    const float4 *qw = tw + qq * LT * 32;
+                    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+                    for (int l = 0; l < LT; ++l) {
+                        uint4 o[4];
+                        float4 w[4];
+#pragma unroll
+                        for (int p = 0; p < 4; ++p) {
+                            o[p] = qo[(l * 4 + p) * 8 + m];
+                            w[p] = qw[(l * 4 + p) * 8 + m];
+                        }
+                        Pack<T, 4> v[16];
+#pragma unroll
+                        for (int p = 0; p < 4; ++p) {
+                            v[p * 4 + 0] = *reinterpret_cast<const Pack<T, 4> *>(vq + (o[p].x + lane_b));
+                            v[p * 4 + 1] = *reinterpret_cast<const Pack<T, 4> *>(vq + (o[p].y + lane_b));
+                            v[p * 4 + 2] = *reinterpret_cast<const Pack<T, 4> *>(vq + (o[p].z + lane_b));
+                            v[p * 4 + 3] = *reinterpret_cast<const Pack<T, 4> *>(vq + (o[p].w + lane_b));
+                        }
+#pragma unroll
+                        for (int p = 0; p < 4; ++p) {
+                            fma4(acc, w[p].x, widen4<T>(v[p * 4 + 0]));
+                            fma4(acc, w[p].y, widen4<T>(v[p * 4 + 1]));
+                            fma4(acc, w[p].z, widen4<T>(v[p * 4 + 2]));
+                            fma4(acc, w[p].w, widen4<T>(v[p * 4 + 3]));
+                        }
+                    }
+                    *reinterpret_cast<Pack<T, 4> *>(out + (long)qi * 256 + lane * 4) = narrow4<T>(acc);
+                }
+            }
+        }
+        dfx::wave_lds_fence();   // the next iteration overwrites the taps
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Generic path: any M, D, L, P; every value dtype (arithmetic in Acc<V>, one rounding at the store).
+// One thread per output element, channel fastest (adjacent lanes read adjacent channels of the same
+// value row), grid-stride.  Used by the reference's tiny test fixture (M=D=2), odd head sizes,
+// unaligned buffers and every fp64 call.
+// ---------------------------------------------------------------------------------------------
+template <typename V>
+__global__ __launch_bounds__(256) void msda_fwd_generic(const V *__restrict__ value,
                                                         const int64_t *__restrict__ shapes,
                                                         const int64_t *__restrict__ lsi,
-                                                        const T *__restrict__ loc,
-                                                        const T *__restrict__ aw, long total, int S,
+                                                        const Acc<V> *__restrict__ loc,
+                                                        const Acc<V> *__restrict__ aw, long total, int S,
                                                         int M, int D, int L, int Lq, int P,
-                                                        T *__restrict__ out)
+                                                        V *__restrict__ out)
 {
+    using T = Acc<V>;
     const int row = M * D;
     for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
          idx += (long)gridDim.x * blockDim.x) {
@@ -236,12 +400,12 @@ __global__ __launch_bounds__(256) void msda_fwd_generic(const T *__restrict__ va
         const int m = (int)(t % M);
         t /= M;
         const int b = (int)(t / Lq);
-        const T *vb = value + (long)b * S * row + m * D + c;
+        const V *vb = value + (long)b * S * row + m * D + c;
         long wp = samp * L * P, lp = wp * 2;
         T col = 0;
         for (int l = 0; l < L; ++l) {
             const int H = (int)shapes[2 * l], W = (int)shapes[2 * l + 1];
-            const T *vl = vb + (long)((int)lsi[l]) * row;
+            const V *vl = vb + (long)((int)lsi[l]) * row;
             for (int p = 0; p < P; ++p, ++wp, lp += 2) {
                 const T h_im = loc[lp + 1] * (T)H - (T)0.5;
                 const T w_im = loc[lp] * (T)W - (T)0.5;
@@ -250,16 +414,79 @@ __global__ __launch_bounds__(256) void msda_fwd_generic(const T *__restrict__ va
                     const int h0 = (int)hf, w0 = (int)wf, h1 = h0 + 1, w1 = w0 + 1;
                     const T lh = h_im - hf, lw = w_im - wf, hh = (T)1 - lh, hw = (T)1 - lw;
                     T v1 = 0, v2 = 0, v3 = 0, v4 = 0;
-                    if (h0 >= 0 && w0 >= 0) v1 = vl[(long)(h0 * W + w0) * row];
-                    if (h0 >= 0 && w1 <= W - 1) v2 = vl[(long)(h0 * W + w1) * row];
-                    if (h1 <= H - 1 && w0 >= 0) v3 = vl[(long)(h1 * W + w0) * row];
-                    if (h1 <= H - 1 && w1 <= W - 1) v4 = vl[(long)(h1 * W + w1) * row];
+                    if (h0 >= 0 && w0 >= 0) v1 = (T)vl[(long)(h0 * W + w0) * row];
+                    if (h0 >= 0 && w1 <= W - 1) v2 = (T)vl[(long)(h0 * W + w1) * row];
+                    if (h1 <= H - 1 && w0 >= 0) v3 = (T)vl[(long)(h1 * W + w0) * row];
+                    if (h1 <= H - 1 && w1 <= W - 1) v4 = (T)vl[(long)(h1 * W + w1) * row];
                     col += (hh * hw * v1 + hh * lw * v2 + lh * hw * v3 + lh * lw * v4) * aw[wp];
                 }
             }
         }
-        out[idx] = col;
+        out[idx] = static_cast<V>(col);
     }
+}
+
+// One host path for every value dtype: argument checks, the empty problem and the generic fallback
+// are shared; the fast paths stay per dtype family (fp32: msda_fwd_taps / msda_fwd_m8d32, bf16 / fp16:
+// msda_half_fwd_taps, fp64: none).  Launch-error texts name the kernel as they always have.
+template <typename V>
+int forward_impl(const V *value, const int64_t *shapes, const int64_t *lsi, const Acc<V> *loc, const Acc<V> *aw,
+                 int N, int S, int M, int D, int L, int Lq, int P, V *out, void *stream)
+{
+    constexpr bool half = sizeof(V) == 2;
+    // an empty value map (S = 0) may come to the 2-byte entry points as a null pointer: nothing of it is read
+    const int rc = dfx::check_dims(half && S == 0 ? static_cast<const void *>(out) : value, shapes, lsi, loc, aw, out,
+                                   N, S, M, D, L, Lq, P);
+    if (rc < 0) return rc;
+    if (rc == 1) return DFX_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const long nq = (long)N * Lq;
+    if (S == 0 || L == 0 || P == 0) {   // nothing to sample: the reference returns zeros
+        if (hipMemsetAsync(out, 0, sizeof(V) * nq * M * D, st) != hipSuccess)
+            return dfx::fail(DFX_ELAUNCH, half ? "msda forward (2-byte value): memset failed"
+                                               : "msda forward: memset failed");
+        return DFX_OK;
+    }
+    if constexpr (!std::is_same<V, double>::value) {   // fp64 always takes the generic kernel
+        // S * 1024 < 2^32 keeps a tap offset plus a second batch element's slab (2-byte wide gather) in 32 bits
+        const bool fast = M == 8 && D == 32 && nq < (1L << 28) && (long)S * 1024 < (1L << 32) &&
+                          dfx::aligned16(value) && dfx::aligned16(out);
+        if (fast && P == 4 && L <= 4 && (reinterpret_cast<uintptr_t>(loc) & 7u) == 0) {
+            // 8 queries per workgroup and iteration; keep >= ~2048 workgroups in the grid when we can
+            int iters = 1;
+            while (iters < 8 && nq / (8L * iters * 2) >= 2048) iters *= 2;
+            const int grid = (int)((nq + 8L * iters - 1) / (8L * iters));
+            const bool wide = half && L == 1 && !dfx::tuning().msda_half_narrow;
+#define DFX_TAPS(K)                                                                                         \
+            hipLaunchKernelGGL(K, dim3(grid), dim3(256), 0, st, value, shapes, lsi, loc, aw, (int)nq, Lq, S, iters, out)
+#define DFX_LAUNCH(LT)                                                                                      \
+            if constexpr (!half) DFX_TAPS((msda_fwd_taps<LT>));                                              \
+            else if (wide) DFX_TAPS((msda_half_fwd_taps<LT, V, true>));                                      \
+            else DFX_TAPS((msda_half_fwd_taps<LT, V, false>))
+            switch (L) {
+                case 1: DFX_LAUNCH(1); break;
+                case 2: DFX_LAUNCH(2); break;
+                case 3: DFX_LAUNCH(3); break;
+                default: DFX_LAUNCH(4); break;
+            }
+#undef DFX_LAUNCH
+#undef DFX_TAPS
+            return dfx::check_launch(half ? "msda_half_fwd_taps" : "msda_fwd_taps");
+        }
+        if constexpr (!half) {
+            if (fast) {
+                const int grid = (int)((nq + 3) / 4);
+                hipLaunchKernelGGL((msda_fwd_m8d32<0, true>), dim3(grid), dim3(256), 0, st, value, shapes, lsi,
+                                   loc, aw, (int)nq, Lq, S, L, P, out);
+                return dfx::check_launch("msda_fwd_m8d32");
+            }
+        }
+    }
+    const long total = nq * M * D;
+    hipLaunchKernelGGL((msda_fwd_generic<V>), dim3(dfx::grid_for(total)), dim3(256), 0, st, value, shapes, lsi, loc,
+                       aw, total, S, M, D, L, Lq, P, out);
+    return dfx::check_launch(half ? "msda_half_fwd_generic"
+                                  : sizeof(V) == 4 ? "msda_fwd_generic<float>" : "msda_fwd_generic<double>");
 }
 
 }  // namespace
@@ -268,59 +495,30 @@ extern "C" int dfx_msda_forward_f32(const float *value, const int64_t *shapes, c
                                     const float *loc, const float *aw, int N, int S, int M, int D,
                                     int L, int Lq, int P, float *out, void *stream)
 {
-    const int rc = dfx::check_dims(value, shapes, lsi, loc, aw, out, N, S, M, D, L, Lq, P);
-    if (rc < 0) return rc;
-    if (rc == 1) return DFX_OK;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const long nq = (long)N * Lq;
-    if (S == 0 || L == 0 || P == 0) {   // nothing to sample: the reference returns zeros
-        if (hipMemsetAsync(out, 0, sizeof(float) * nq * M * D, st) != hipSuccess)
-            return dfx::fail(DFX_ELAUNCH, "msda forward: memset failed");
-        return DFX_OK;
-    }
-    const bool fast = M == 8 && D == 32 && nq < (1L << 28) && (long)S * 1024 < (1L << 32) &&
-                      dfx::aligned16(value) && dfx::aligned16(out);
-    if (fast && P == 4 && L <= 4 && (reinterpret_cast<uintptr_t>(loc) & 7u) == 0) {
-        // 8 queries per workgroup and iteration; keep >= ~2048 workgroups in the grid when we can
-        int iters = 1;
-        while (iters < 8 && nq / (8L * iters * 2) >= 2048) iters *= 2;
-        const int grid = (int)((nq + 8L * iters - 1) / (8L * iters));
-#define DFX_LAUNCH(LT)                                                                              \
-        hipLaunchKernelGGL((msda_fwd_taps<LT>), dim3(grid), dim3(256), 0, st, value, shapes, lsi, loc, \
-                           aw, (int)nq, Lq, S, iters, out)
-        switch (L) {
-            case 1: DFX_LAUNCH(1); break;
-            case 2: DFX_LAUNCH(2); break;
-            case 3: DFX_LAUNCH(3); break;
-            default: DFX_LAUNCH(4); break;
-        }
-#undef DFX_LAUNCH
-        return dfx::check_launch("msda_fwd_taps");
-    }
-    if (fast) {
-        const int grid = (int)((nq + 3) / 4);
-        hipLaunchKernelGGL((msda_fwd_m8d32<0, true>), dim3(grid), dim3(256), 0, st, value, shapes, lsi,
-                           loc, aw, (int)nq, Lq, S, L, P, out);
-        return dfx::check_launch("msda_fwd_m8d32");
-    }
-    const long total = nq * M * D;
-    hipLaunchKernelGGL((msda_fwd_generic<float>), dim3(dfx::grid_for(total)), dim3(256), 0, st, value, shapes, lsi, loc,
-                       aw, total, S, M, D, L, Lq, P, out);
-    return dfx::check_launch("msda_fwd_generic<float>");
+    return forward_impl<float>(value, shapes, lsi, loc, aw, N, S, M, D, L, Lq, P, out, stream);
 }
 
 extern "C" int dfx_msda_forward_f64(const double *value, const int64_t *shapes, const int64_t *lsi,
                                     const double *loc, const double *aw, int N, int S, int M, int D,
                                     int L, int Lq, int P, double *out, void *stream)
 {
-    const int rc = dfx::check_dims(value, shapes, lsi, loc, aw, out, N, S, M, D, L, Lq, P);
-    if (rc < 0) return rc;
-    if (rc == 1) return DFX_OK;
-    const long total = (long)N * Lq * M * D;
-    hipLaunchKernelGGL((msda_fwd_generic<double>), dim3(dfx::grid_for(total)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), value, shapes, lsi, loc, aw, total, S, M, D, L,
-                       Lq, P, out);
-    return dfx::check_launch("msda_fwd_generic<double>");
+    return forward_impl<double>(value, shapes, lsi, loc, aw, N, S, M, D, L, Lq, P, out, stream);
+}
+
+extern "C" int dfx_msda_forward_bf16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
+                                     const float *loc, const float *aw, int N, int S, int M, int D, int L, int Lq,
+                                     int P, uint16_t *out, void *stream)
+{
+    return forward_impl<__hip_bfloat16>(reinterpret_cast<const __hip_bfloat16 *>(value), shapes, lsi, loc, aw, N, S,
+                                        M, D, L, Lq, P, reinterpret_cast<__hip_bfloat16 *>(out), stream);
+}
+
+extern "C" int dfx_msda_forward_f16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
+                                    const float *loc, const float *aw, int N, int S, int M, int D, int L, int Lq,
+                                    int P, uint16_t *out, void *stream)
+{
+    return forward_impl<_Float16>(reinterpret_cast<const _Float16 *>(value), shapes, lsi, loc, aw, N, S, M, D, L,
+                                  Lq, P, reinterpret_cast<_Float16 *>(out), stream);
 }
 
 extern "C" int dfx_abi_version(void) { return 4; }

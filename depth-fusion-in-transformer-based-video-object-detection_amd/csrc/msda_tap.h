@@ -7,10 +7,45 @@
 // Taps are computed ONCE per (query, head, point) by one lane - not redundantly by the 8 lanes
 // that share a head - staged in LDS in [query][level][point][head] order, and read back by the
 // gather phase as two conflict-free 16-byte broadcasts per point.
+//
+// Also the value-dtype helpers of the MSDA kernels (fp32, fp64, bf16, fp16): the arithmetic type of
+// a value dtype and the packed 2-byte channel loads / stores.
 #pragma once
+#include <hip/hip_bf16.h>
+
+#include <type_traits>
+
 #include "dfx_common.h"
 
 namespace dfx {
+
+// Arithmetic type of an MSDA kernel with value dtype V: double for fp64, float for fp32, bf16 and fp16
+// (a 2-byte value is widened on load; locations, weights and gradients are fp32).
+template <typename V>
+using Acc = typename std::conditional<std::is_same<V, double>::value, double, float>::type;
+
+// K consecutive 2-byte channels, loaded / stored as one 2K-byte access
+template <typename T, int K>
+struct alignas(2 * K) Pack {
+    T v[K];
+};
+
+template <typename T>
+__device__ __forceinline__ float4 widen4(const Pack<T, 4> &p)
+{
+    return make_float4((float)p.v[0], (float)p.v[1], (float)p.v[2], (float)p.v[3]);
+}
+
+template <typename T>
+__device__ __forceinline__ Pack<T, 4> narrow4(const float4 &a)
+{
+    Pack<T, 4> p;
+    p.v[0] = static_cast<T>(a.x);
+    p.v[1] = static_cast<T>(a.y);
+    p.v[2] = static_cast<T>(a.z);
+    p.v[3] = static_cast<T>(a.w);
+    return p;
+}
 
 struct Tap {
     uint4 off;    // byte offsets of the corners (y0,x0) (y0,x1) (y1,x0) (y1,x1)

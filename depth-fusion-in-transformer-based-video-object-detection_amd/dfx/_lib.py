@@ -17,7 +17,7 @@ SIGNATURES = {
     "dfx_msda_forward_f64": [_p] * 5 + _DIMS + [_p, _p],
     "dfx_msda_backward_f32": [_p] * 6 + _DIMS + [_p, _p, _p, _p],
     "dfx_msda_backward_f64": [_p] * 6 + _DIMS + [_p, _p, _p, _p],
-    # 2-byte value / grad_out / out, fp32 loc / aw / gradients (csrc/msda_half.hip)
+    # 2-byte value / grad_out / out, fp32 loc / aw / gradients (csrc/msda_forward.hip, csrc/msda_backward.hip)
     "dfx_msda_forward_bf16": [_p] * 5 + _DIMS + [_p, _p],
     "dfx_msda_forward_f16": [_p] * 5 + _DIMS + [_p, _p],
     "dfx_msda_backward_bf16": [_p] * 6 + _DIMS + [_p, _p, _p, _p],

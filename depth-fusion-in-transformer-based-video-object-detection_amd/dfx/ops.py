@@ -12,7 +12,7 @@ import torch
 from . import _lib
 
 _SUFFIX = {torch.float32: "f32", torch.float64: "f64"}
-# 2-byte value maps (mixed precision, csrc/msda_half.hip): sampling_loc and attn_weight stay fp32
+# 2-byte value maps (mixed precision, csrc/msda_forward.hip / msda_backward.hip): sampling_loc and attn_weight stay fp32
 _HALF_SUFFIX = {torch.bfloat16: "bf16", torch.float16: "f16"}
 ACT = {None: 0, "none": 0, "relu": 1, "gelu": 2}
 

@@ -1,5 +1,6 @@
-"""CPU: the 2-byte value entry points of include/dfx_msda.h (csrc/msda_half.hip) are declared with fp32 locations and
-weights, bound in dfx/_lib.py, exported by the library, and the CPU-tensor rule of the operator covers them."""
+"""CPU: the 2-byte value entry points of include/dfx_msda.h (csrc/msda_forward.hip, csrc/msda_backward.hip) are
+declared with fp32 locations and weights, bound in dfx/_lib.py, exported by the library, and the CPU-tensor rule of the
+operator covers them."""
 import ctypes
 import os
 import re

@@ -1,6 +1,6 @@
 """GPU: the MSDA operator with a bf16 / fp16 value map and fp32 sampling locations and attention weights
-(csrc/msda_half.hip; include/dfx_msda.h, dfx_msda_forward_bf16 ...) - what MSDeformAttn hands the op under
-torch.autocast.
+(csrc/msda_forward.hip, csrc/msda_backward.hip; include/dfx_msda.h, dfx_msda_forward_bf16 ...) - what MSDeformAttn
+hands the op under torch.autocast.
 
 References are the CPU oracle in fp64 on the half inputs upcast exactly.  u is the unit roundoff of the value
 dtype (2^-8 bf16, 2^-11 fp16): half outputs and grad_value within rtol = 2u, atol = 1e-5 * max|ref|; fp32 grad_loc /
