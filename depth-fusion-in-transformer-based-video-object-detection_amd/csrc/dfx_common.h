@@ -69,7 +69,7 @@ struct Tuning {
     bool level_not_persistent = false;  // DFX_LEVEL_NOT_PERSISTENT
     bool level_variant_set = false;  // DFX_LEVEL_VARIANT given
     int level_variant = 0;           // DFX_LEVEL_VARIANT: kernel variant of msda_level.hip (A/B)
-    bool msda_half_narrow = false;   // DFX_MSDA_HALF_NARROW: 8-byte (8 lanes per head) gather of msda_half_fwd_taps at L = 1 too (A/B)
+    bool msda_half_narrow = false;   // DFX_MSDA_HALF_NARROW: 8-byte (8 lanes per head) gather of the 2-byte msda_fwd_taps at L = 1 too (A/B)
     void read()
     {
         *this = Tuning();

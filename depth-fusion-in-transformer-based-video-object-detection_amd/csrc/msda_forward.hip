@@ -6,7 +6,8 @@
 // The reference gives one THREAD one output channel (1024-thread blocks, int64 shape loads and
 // scalar 4-byte gathers per thread, every thread redoing the sample geometry).  Here the unit of
 // work is a WAVE and the work is split in two phases (production geometry M=8 heads x D=32
-// channels, P=4 points, fp32):
+// channels, P=4 points; msda_fwd_taps<LT, V, WIDE> for a value map of dtype V = fp32, bf16 or fp16,
+// locations and weights always fp32; the figures below are the fp32 ones):
 //
 //   phase A  "taps": lane = one (query, level, point, head) sample of the wave's 2 queries.  It
 //            loads its (x, y, weight) triple - the 64 lanes read 768 contiguous bytes - and does
@@ -19,13 +20,16 @@
 //            with a wave-uniform base + 32-bit offset; the 8 lanes of a head read one contiguous
 //            128-byte value row, so a wave-instruction touches 8 rows.  16 gathers per level are
 //            in flight before the first FMA; the reduction over L*P samples stays in registers
-//            and the query's 1 KiB output row leaves as one float4 per lane.
+//            and the query's 1 KiB output row leaves as one float4 per lane.  (msda_tap.h,
+//            gather_query; a 2-byte V halves every size here: 512-byte token rows, 8-byte loads,
+//            64-byte head rows, and it has a second, 16-byte gather - see below.)
 //
 // A 256-thread workgroup holds 4 waves x 2 queries = 8 consecutive queries (x `iters`);
 // workgroups are remapped so that each XCD walks a contiguous raster range of queries and its
 // private L2 holds only that band of the value map (dfx_common.h).  The earlier one-phase form
 // (every lane redoing the geometry) measured VALU-bound at ~1000 instructions per query; it is
-// kept below only for P != 4.
+// kept (msda_fwd_m8d32) only for what the taps kernel does not take: P != 4, L > 4, a loc that is
+// not 8-byte aligned.
 //
 // Roofline: HBM-bound gather.  Algorithmic bytes per call
 //   4 * (N*S*M*D  +  3*N*Lq*M*L*P  +  N*Lq*M*D)       (value + loc/aw + out, fp32)
@@ -39,15 +43,16 @@
 // (a plain conversion, v_cvt_pk_{bf16,f16}_f32).  Backward accumulates grad_value into an fp32
 // buffer with float atomics (a packed 2-byte atomic would round at every add).
 //
-//   forward, M = 8, D = 32, P = 4, L <= 4, 16-byte aligned value / out: msda_half_fwd_taps.  Phase A
-//            is msda_fwd_taps' (msda_tap.h, write_taps with 512-byte token rows); phase B gathers
-//            each corner as 2-byte channels, accumulates in fp32 registers and stores the output
-//            row in the value dtype.  Two gather widths, the same bits:
+//   forward, M = 8, D = 32, P = 4, L <= 4, 16-byte aligned value / out: msda_fwd_taps<LT, bf16 / fp16>, the
+//            kernel above (launch errors name it msda_half_fwd_taps, as they always have).  Phase A is the
+//            same code with 512-byte token rows; phase B gathers each corner as 2-byte channels, accumulates
+//            in fp32 registers and stores the output row in the value dtype.  Two gather widths, the same bits:
 //              wide    4 lanes x 16 B per head: 8 channels a lane, both queries of the wave in one pass
 //              narrow  8 lanes x  8 B per head: 4 channels a lane, one query per pass (the fp32 mapping)
 //            wide for L = 1 (bf16, 32 frames: enc 98 us against 130, dec 12.9 against 14.2), narrow for more
 //            levels (enc L4: 601 us against 621; wide holds 16 corner rows of 16 B per level in flight and
-//            needs 178-256 VGPRs at L >= 2).  DFX_MSDA_HALF_NARROW=1 takes narrow for every L (A/B).
+//            needs 178-256 VGPRs at L >= 2, so it is built for L = 1 only).  DFX_MSDA_HALF_NARROW=1 takes
+//            narrow for every L (A/B).
 //   forward, anything else: msda_fwd_generic<bf16 / fp16>, one thread per output element, scalar 2-byte
 //            reads (odd D, any alignment).
 //   backward (msda_backward.hip), M = 8, D = 32, 16-byte aligned value / grad_out: msda_bwd_m8d32<bf16 /
@@ -61,125 +66,69 @@
 namespace {
 
 using dfx::Acc;
+using dfx::fma4;
 using dfx::narrow4;
 using dfx::Pack;
-using dfx::widen4;
+using dfx::Tap;
 using dfx::xcd_remap;
 
-struct Corner4 {
-    int o00, o01, o10, o11;      // element offsets (in floats) of the 4 corners inside one level
-    float w00, w01, w10, w11;    // bilinear weights, already multiplied by the attention weight
-};
-
-// Geometry of one sample.  Follows ms_deform_im2col_cuda.cuh:281-291 (pixel coords, skip rule)
-// and :33-84 (corner validity, weights).  Invalid corners / skipped samples get weight 0 and a
-// clamped (always in-bounds) address.
-__device__ __forceinline__ Corner4 corners(float lx, float ly, float a, int H, int W, int row_stride)
-{
-    const float h_im = ly * (float)H - 0.5f;
-    const float w_im = lx * (float)W - 0.5f;
-    const bool inr = (h_im > -1.f) && (w_im > -1.f) && (h_im < (float)H) && (w_im < (float)W);
-    // clamp in float first: keeps the float->int conversion defined for NaN / huge inputs
-    const float hf = floorf(fminf(fmaxf(h_im, -1.f), (float)H));
-    const float wf = floorf(fminf(fmaxf(w_im, -1.f), (float)W));
-    const int h0 = (int)hf, w0 = (int)wf;
-    const int h1 = h0 + 1, w1 = w0 + 1;
-    const float lh = h_im - hf, lw = w_im - wf;
-    const float hh = 1.f - lh, hw = 1.f - lw;
-    const bool top = inr && h0 >= 0, bot = inr && h1 <= H - 1, lef = w0 >= 0, rig = w1 <= W - 1;
-    Corner4 c;
-    c.w00 = (top && lef) ? hh * hw * a : 0.f;
-    c.w01 = (top && rig) ? hh * lw * a : 0.f;
-    c.w10 = (bot && lef) ? lh * hw * a : 0.f;
-    c.w11 = (bot && rig) ? lh * lw * a : 0.f;
-    const int y0 = min(max(h0, 0), H - 1), y1 = min(max(h1, 0), H - 1);
-    const int x0 = min(max(w0, 0), W - 1), x1 = min(max(w1, 0), W - 1);
-    c.o00 = (y0 * W + x0) * row_stride;
-    c.o01 = (y0 * W + x1) * row_stride;
-    c.o10 = (y1 * W + x0) * row_stride;
-    c.o11 = (y1 * W + x1) * row_stride;
-    return c;
-}
-
-using dfx::fma4;
-using dfx::Tap;
-
 // ---------------------------------------------------------------------------------------------
-// Fast path: M = 8, D = 32, fp32, 16-byte aligned buffers.  PT = points per level at compile
-// time (4 in every shipped config); PT = 0 keeps P a run-time value (scalar loc/aw loads).
+// Fast path: M = 8, D = 32, fp32, 16-byte aligned buffers, any P and L (run-time values; scalar
+// loc / aw loads).  One phase: a wave = one query, lane = (head, channel quad), every lane does the
+// geometry of its head's samples itself.
 // ---------------------------------------------------------------------------------------------
-template <int PT, bool REMAP>
 __global__ __launch_bounds__(256) void msda_fwd_m8d32(const float *__restrict__ value,
                                                       const int64_t *__restrict__ shapes,
                                                       const int64_t *__restrict__ lsi,
                                                       const float *__restrict__ loc,
                                                       const float *__restrict__ aw,
-                                                      int NQ, int Lq, int S, int L, int Prt,
+                                                      int NQ, int Lq, int S, int L, int P,
                                                       float *__restrict__ out)
 {
-    const int blk = REMAP ? xcd_remap(blockIdx.x, gridDim.x) : blockIdx.x;
+    const int blk = xcd_remap(blockIdx.x, gridDim.x);
     const int lane = threadIdx.x & 63;
     const int qi = blk * 4 + (threadIdx.x >> 6);   // flat query index over N*Lq
     if (qi >= NQ) return;
-    const int P = PT ? PT : Prt;
     const int m = lane >> 3, cg = lane & 7;
-    const int b = qi / Lq;
     const long samp = (long)qi * 8 + m;            // flat (b,q,m) index
-    const float *vb = value + (long)b * S * 256 + m * 32 + cg * 4;
+    // the batch element's slab, plus this lane's channel quad inside a head's 128 bytes
+    const char *vb = reinterpret_cast<const char *>(value) + (size_t)(qi / Lq) * S * 1024 + cg * 16;
     const float *lp = loc + samp * (long)(L * P * 2);
     const float *ap = aw + samp * (long)(L * P);
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
 
     for (int l = 0; l < L; ++l) {
-        const int H = (int)shapes[2 * l], W = (int)shapes[2 * l + 1];
-        const float *vl = vb + (long)((int)lsi[l]) * 256;
-        if (H <= 0 || W <= 0) continue;   // empty level: nothing can be in range
-        if (PT == 4) {
-            const float4 la = *reinterpret_cast<const float4 *>(lp + l * 8);
-            const float4 lb = *reinterpret_cast<const float4 *>(lp + l * 8 + 4);
-            const float4 a4 = *reinterpret_cast<const float4 *>(ap + l * 4);
-            const Corner4 c0 = corners(la.x, la.y, a4.x, H, W, 256);
-            const Corner4 c1 = corners(la.z, la.w, a4.y, H, W, 256);
-            const Corner4 c2 = corners(lb.x, lb.y, a4.z, H, W, 256);
-            const Corner4 c3 = corners(lb.z, lb.w, a4.w, H, W, 256);
-#define DFX_LD(c, o) (*reinterpret_cast<const float4 *>(vl + c.o))
-            const float4 v00 = DFX_LD(c0, o00), v01 = DFX_LD(c0, o01), v02 = DFX_LD(c0, o10), v03 = DFX_LD(c0, o11);
-            const float4 v10 = DFX_LD(c1, o00), v11 = DFX_LD(c1, o01), v12 = DFX_LD(c1, o10), v13 = DFX_LD(c1, o11);
-            const float4 v20 = DFX_LD(c2, o00), v21 = DFX_LD(c2, o01), v22 = DFX_LD(c2, o10), v23 = DFX_LD(c2, o11);
-            const float4 v30 = DFX_LD(c3, o00), v31 = DFX_LD(c3, o01), v32 = DFX_LD(c3, o10), v33 = DFX_LD(c3, o11);
-#undef DFX_LD
-            fma4(acc, c0.w00, v00); fma4(acc, c0.w01, v01); fma4(acc, c0.w10, v02); fma4(acc, c0.w11, v03);
-            fma4(acc, c1.w00, v10); fma4(acc, c1.w01, v11); fma4(acc, c1.w10, v12); fma4(acc, c1.w11, v13);
-            fma4(acc, c2.w00, v20); fma4(acc, c2.w01, v21); fma4(acc, c2.w10, v22); fma4(acc, c2.w11, v23);
-            fma4(acc, c3.w00, v30); fma4(acc, c3.w01, v31); fma4(acc, c3.w10, v32); fma4(acc, c3.w11, v33);
-        } else {
-            for (int p = 0; p < P; ++p) {
-                const float lx = lp[(l * P + p) * 2], ly = lp[(l * P + p) * 2 + 1];
-                const Corner4 c = corners(lx, ly, ap[l * P + p], H, W, 256);
-                const float4 v0 = *reinterpret_cast<const float4 *>(vl + c.o00);
-                const float4 v1 = *reinterpret_cast<const float4 *>(vl + c.o01);
-                const float4 v2 = *reinterpret_cast<const float4 *>(vl + c.o10);
-                const float4 v3 = *reinterpret_cast<const float4 *>(vl + c.o11);
-                fma4(acc, c.w00, v0); fma4(acc, c.w01, v1); fma4(acc, c.w10, v2); fma4(acc, c.w11, v3);
-            }
+        const int H = (int)shapes[2 * l], W = (int)shapes[2 * l + 1], R = (int)lsi[l];
+        for (int p = 0; p < P; ++p) {
+            const float lx = lp[(l * P + p) * 2], ly = lp[(l * P + p) * 2 + 1];
+            const Tap t = dfx::make_tap<1024u>(lx, ly, ap[l * P + p], H, W, R, m * 128);
+            const float4 v0 = *reinterpret_cast<const float4 *>(vb + t.off.x);
+            const float4 v1 = *reinterpret_cast<const float4 *>(vb + t.off.y);
+            const float4 v2 = *reinterpret_cast<const float4 *>(vb + t.off.z);
+            const float4 v3 = *reinterpret_cast<const float4 *>(vb + t.off.w);
+            fma4(acc, t.w.x, v0); fma4(acc, t.w.y, v1); fma4(acc, t.w.z, v2); fma4(acc, t.w.w, v3);
         }
     }
     *reinterpret_cast<float4 *>(out + (long)qi * 256 + m * 32 + cg * 4) = acc;
 }
 
 // ---------------------------------------------------------------------------------------------
-// Fast path: M = 8, D = 32, P = 4, fp32, LT levels (1..4) known at compile time.
+// Fast path: M = 8, D = 32, P = 4, LT levels (1..4) known at compile time; value / out of dtype V
+// (fp32, bf16, fp16), fp32 loc / aw.  Token rows are 256 * sizeof(V) bytes.  A 256-thread
+// workgroup = 4 waves x 2 queries.  WIDE (2-byte V, LT = 1 only) is the 16-byte gather.
 // ---------------------------------------------------------------------------------------------
-template <int LT>
-__global__ __launch_bounds__(256) void msda_fwd_taps(const float *__restrict__ value,
+template <int LT, typename V, bool WIDE>
+__global__ __launch_bounds__(256) void msda_fwd_taps(const V *__restrict__ value,
                                                      const int64_t *__restrict__ shapes,
                                                      const int64_t *__restrict__ lsi,
                                                      const float *__restrict__ loc,
                                                      const float *__restrict__ aw, int NQ, int Lq,
-                                                     int S, int iters, float *__restrict__ out)
+                                                     int S, int iters, V *__restrict__ out)
 {
+    static_assert(!WIDE || (LT == 1 && sizeof(V) == 2), "the wide gather serves 2-byte values at L = 1 only");
     constexpr int QW = 2;                 // queries per wave per iteration
     constexpr int TAPS = QW * LT * 32;    // taps per wave per iteration (multiple of 64)
+    constexpr unsigned ROW = 256u * sizeof(V);   // bytes of one token row (8 heads x 32 channels)
     __shared__ uint4 s_off[4][TAPS];
     __shared__ float4 s_w[4][TAPS];
     // wave index as a scalar: everything derived from it (query index, batch element, the value
@@ -188,80 +137,7 @@ __global__ __launch_bounds__(256) void msda_fwd_taps(const float *__restrict__ v
     uint4 *toff = s_off[wave];
     float4 *tw = s_w[wave];
     const int blk = xcd_remap(blockIdx.x, gridDim.x);
-    const int m = lane >> 3;
-    const unsigned lane_b = (unsigned)(lane & 7) * 16u;
-
-    int Hs[LT], Ws[LT], Rs[LT];
-#pragma unroll
-    for (int l = 0; l < LT; ++l) {
-        Hs[l] = (int)shapes[2 * l];
-        Ws[l] = (int)shapes[2 * l + 1];
-        Rs[l] = (int)lsi[l];
-    }
-
-    for (int it = 0; it < iters; ++it) {
-        const int q0 = ((blk * iters + it) * 4 + wave) * QW;   // first query of this wave (uniform)
-        if (q0 >= NQ) break;
-        // ---- phase A: one tap per lane ----
-#pragma unroll
-        for (int c = 0; c < TAPS / 64; ++c) {
-            const int s = c * 64 + lane;                 // slot = ((qq*LT + l)*4 + p)*8 + head
-            const int hm = s & 7, p = (s >> 3) & 3, ql = s >> 5;
-            const int l = (LT == 1) ? 0 : ql % LT, qq = (LT == 1) ? ql : ql / LT;
-            const int qi = q0 + qq;
-            Tap t;
-            if (qi < NQ) {
-                const long e = (((long)qi * 8 + hm) * LT + l) * 4 + p;
-                const float2 xy = *reinterpret_cast<const float2 *>(loc + e * 2);
-                int H = Hs[0], W = Ws[0], R = Rs[0];
-#pragma unroll
-                for (int k = 1; k < LT; ++k)
-                    if (l == k) { H = Hs[k]; W = Ws[k]; R = Rs[k]; }
-                t = dfx::make_tap(xy.x, xy.y, aw[e], H, W, R, hm * 128);
-            } else {
-                t.off = make_uint4(0u, 0u, 0u, 0u);
-                t.w = make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-            toff[s] = t.off;
-            tw[s] = t.w;
-        }
-        dfx::wave_lds_fence();
-        // ---- phase B: gather, one query at a time ----
-#pragma unroll
-        for (int qq = 0; qq < QW; ++qq) {
-            const int qi = q0 + qq;
-            if (qi < NQ) {
-                const int b = qi / Lq;
-                const char *vb = reinterpret_cast<const char *>(value) + (size_t)b * S * 1024;
-                const float4 acc = dfx::gather_query<LT>(vb, lane_b, m, toff + qq * LT * 32, tw + qq * LT * 32);
-                *reinterpret_cast<float4 *>(out + (long)qi * 256 + lane * 4) = acc;
-            }
-        }
-        dfx::wave_lds_fence();   // the next iteration overwrites the taps
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// Forward fast path: M = 8, D = 32, P = 4, LT levels (1..4), 2-byte value / out, fp32 loc / aw.
-// Token rows are 512 bytes (8 heads x 64 B).  A 256-thread workgroup = 4 waves x 2 queries.
-// ---------------------------------------------------------------------------------------------
-template <int LT, typename T, bool WIDE>
-__global__ __launch_bounds__(256) void msda_half_fwd_taps(const T *__restrict__ value,
-                                                          const int64_t *__restrict__ shapes,
-                                                          const int64_t *__restrict__ lsi,
-                                                          const float *__restrict__ loc,
-                                                          const float *__restrict__ aw, int NQ, int Lq,
-                                                          int S, int iters, T *__restrict__ out)
-{
-    constexpr int QW = 2;                 // queries per wave per iteration
-    constexpr int TAPS = QW * LT * 32;
-    __shared__ uint4 s_off[4][TAPS];
-    __shared__ float4 s_w[4][TAPS];
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    uint4 *toff = s_off[wave];
-    float4 *tw = s_w[wave];
-    const int blk = xcd_remap(blockIdx.x, gridDim.x);
-    const unsigned slab = (unsigned)S * 512u;     // bytes of one batch element's value map
+    const unsigned slab = (unsigned)S * ROW;      // bytes of one batch element's value map
 
     dfx::LevelDims<LT> lv;
 #pragma unroll
@@ -275,15 +151,15 @@ __global__ __launch_bounds__(256) void msda_half_fwd_taps(const T *__restrict__ 
         const int q0 = ((blk * iters + it) * 4 + wave) * QW;   // first query of this wave (uniform)
         if (q0 >= NQ) break;
         // ---- phase A: one tap per lane ----
-        dfx::write_taps<LT, QW, 512u>(loc, aw, q0, NQ, lane, lv, toff, tw);
+        dfx::write_taps<LT, QW, ROW>(loc, aw, q0, NQ, lane, lv, toff, tw);
         dfx::wave_lds_fence();
         // ---- phase B: gather ----
-        const int b0 = q0 / Lq;
-        const char *vb = reinterpret_cast<const char *>(value) + (size_t)b0 * slab;
         if (WIDE) {
             // lane = (query qq = lane>>5, head m = (lane>>2)&7, channel octet cg = lane&3); the pair may
             // straddle two batch elements, so the second one's slab goes into the lane's offset
             // (< 2 * slab <= S * 1024 < 2^32: the launcher's bound).  A query past NQ has zero taps.
+            const int b0 = q0 / Lq;
+            const char *vb = reinterpret_cast<const char *>(value) + (size_t)b0 * slab;
             const int qq = lane >> 5, m = (lane >> 2) & 7;
             const int qi = q0 + qq;
             const int b = qi < NQ ? qi / Lq : b0;
@@ -300,73 +176,46 @@ __global__ __launch_bounds__(256) void msda_half_fwd_taps(const T *__restrict__ 
                     o[p] = qo[(l * 4 + p) * 8 + m];
                     w[p] = qw[(l * 4 + p) * 8 + m];
                 }
-                Pack<T, 8> v[16];
+                Pack<V, 8> v[16];
 #pragma unroll
                 for (int p = 0; p < 4; ++p) {
-                    v[p * 4 + 0] = *reinterpret_cast<const Pack<T, 8> *>(vb + (o[p].x + lane_b));
-                    v[p * 4 + 1] = *reinterpret_cast<const Pack<T, 8> *>(vb + (o[p].y + lane_b));
-                    v[p * 4 + 2] = *reinterpret_cast<const Pack<T, 8> *>(vb + (o[p].z + lane_b));
-                    v[p * 4 + 3] = *reinterpret_cast<const Pack<T, 8> *>(vb + (o[p].w + lane_b));
+                    v[p * 4 + 0] = *reinterpret_cast<const Pack<V, 8> *>(vb + (o[p].x + lane_b));
+                    v[p * 4 + 1] = *reinterpret_cast<const Pack<V, 8> *>(vb + (o[p].y + lane_b));
+                    v[p * 4 + 2] = *reinterpret_cast<const Pack<V, 8> *>(vb + (o[p].z + lane_b));
+                    v[p * 4 + 3] = *reinterpret_cast<const Pack<V, 8> *>(vb + (o[p].w + lane_b));
                 }
 #pragma unroll
                 for (int p = 0; p < 4; ++p) {
                     const float wk[4] = {w[p].x, w[p].y, w[p].z, w[p].w};
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
-                        const Pack<T, 8> &c = v[p * 4 + k];
+                        const Pack<V, 8> &c = v[p * 4 + k];
                         fma4(lo, wk[k], make_float4((float)c.v[0], (float)c.v[1], (float)c.v[2], (float)c.v[3]));
                         fma4(hi, wk[k], make_float4((float)c.v[4], (float)c.v[5], (float)c.v[6], (float)c.v[7]));
                     }
                 }
             }
             if (qi < NQ) {
-                const Pack<T, 4> a = narrow4<T>(lo), c = narrow4<T>(hi);
-                Pack<T, 8> r;
+                const Pack<V, 4> a = narrow4<V>(lo), c = narrow4<V>(hi);
+                Pack<V, 8> r;
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     r.v[k] = a.v[k];
                     r.v[4 + k] = c.v[k];
                 }
-                *reinterpret_cast<Pack<T, 8> *>(out + (long)qi * 256 + (lane & 31) * 8) = r;
+                *reinterpret_cast<Pack<V, 8> *>(out + (long)qi * 256 + (lane & 31) * 8) = r;
             }
         } else {
             // lane = (head m = lane>>3, channel quad cg = lane&7), one query per pass
             const int m = lane >> 3;
-            const unsigned lane_b = (unsigned)(lane & 7) * 8u;
+            const unsigned lane_b = (unsigned)(lane & 7) * (unsigned)(4 * sizeof(V));
 #pragma unroll
             for (int qq = 0; qq < QW; ++qq) {
                 const int qi = q0 + qq;
                 if (qi < NQ) {
                     const char *vq = reinterpret_cast<const char *>(value) + (size_t)(qi / Lq) * slab;
-                    const uint4 *qo = toff + qq * LT * 32;
-                    const float4 *qw = tw + qq * LT * 32;
-                    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-                    for (int l = 0; l < LT; ++l) {
-                        uint4 o[4];
-                        float4 w[4];
-#pragma unroll
-                        for (int p = 0; p < 4; ++p) {
-                            o[p] = qo[(l * 4 + p) * 8 + m];
-                            w[p] = qw[(l * 4 + p) * 8 + m];
-                        }
-                        Pack<T, 4> v[16];
-#pragma unroll
-                        for (int p = 0; p < 4; ++p) {
-                            v[p * 4 + 0] = *reinterpret_cast<const Pack<T, 4> *>(vq + (o[p].x + lane_b));
-                            v[p * 4 + 1] = *reinterpret_cast<const Pack<T, 4> *>(vq + (o[p].y + lane_b));
-                            v[p * 4 + 2] = *reinterpret_cast<const Pack<T, 4> *>(vq + (o[p].z + lane_b));
-                            v[p * 4 + 3] = *reinterpret_cast<const Pack<T, 4> *>(vq + (o[p].w + lane_b));
-                        }
-#pragma unroll
-                        for (int p = 0; p < 4; ++p) {
-                            fma4(acc, w[p].x, widen4<T>(v[p * 4 + 0]));
-                            fma4(acc, w[p].y, widen4<T>(v[p * 4 + 1]));
-                            fma4(acc, w[p].z, widen4<T>(v[p * 4 + 2]));
-                            fma4(acc, w[p].w, widen4<T>(v[p * 4 + 3]));
-                        }
-                    }
-                    *reinterpret_cast<Pack<T, 4> *>(out + (long)qi * 256 + lane * 4) = narrow4<T>(acc);
+                    const float4 acc = dfx::gather_query<LT, V>(vq, lane_b, m, toff + qq * LT * 32, tw + qq * LT * 32);
+                    *reinterpret_cast<Pack<V, 4> *>(out + (long)qi * 256 + lane * 4) = narrow4<V>(acc);
                 }
             }
         }
@@ -427,8 +276,8 @@ __global__ __launch_bounds__(256) void msda_fwd_generic(const V *__restrict__ va
 }
 
 // One host path for every value dtype: argument checks, the empty problem and the generic fallback
-// are shared; the fast paths stay per dtype family (fp32: msda_fwd_taps / msda_fwd_m8d32, bf16 / fp16:
-// msda_half_fwd_taps, fp64: none).  Launch-error texts name the kernel as they always have.
+// are shared, and so is the taps fast path of fp32, bf16 and fp16 (fp32 alone has msda_fwd_m8d32 behind it,
+// fp64 has no fast path).  Launch-error texts name the kernel as they always have.
 template <typename V>
 int forward_impl(const V *value, const int64_t *shapes, const int64_t *lsi, const Acc<V> *loc, const Acc<V> *aw,
                  int N, int S, int M, int D, int L, int Lq, int P, V *out, void *stream)
@@ -457,26 +306,27 @@ int forward_impl(const V *value, const int64_t *shapes, const int64_t *lsi, cons
             while (iters < 8 && nq / (8L * iters * 2) >= 2048) iters *= 2;
             const int grid = (int)((nq + 8L * iters - 1) / (8L * iters));
             const bool wide = half && L == 1 && !dfx::tuning().msda_half_narrow;
-#define DFX_TAPS(K)                                                                                         \
-            hipLaunchKernelGGL(K, dim3(grid), dim3(256), 0, st, value, shapes, lsi, loc, aw, (int)nq, Lq, S, iters, out)
-#define DFX_LAUNCH(LT)                                                                                      \
-            if constexpr (!half) DFX_TAPS((msda_fwd_taps<LT>));                                              \
-            else if (wide) DFX_TAPS((msda_half_fwd_taps<LT, V, true>));                                      \
-            else DFX_TAPS((msda_half_fwd_taps<LT, V, false>))
-            switch (L) {
-                case 1: DFX_LAUNCH(1); break;
-                case 2: DFX_LAUNCH(2); break;
-                case 3: DFX_LAUNCH(3); break;
-                default: DFX_LAUNCH(4); break;
+#define DFX_TAPS(LT, WIDE)                                                                                  \
+            hipLaunchKernelGGL((msda_fwd_taps<LT, V, WIDE>), dim3(grid), dim3(256), 0, st, value, shapes, lsi, loc, \
+                               aw, (int)nq, Lq, S, iters, out)
+            if constexpr (half) {   // the wide gather is built for 2-byte values at L = 1 only
+                if (wide) DFX_TAPS(1, true);
             }
-#undef DFX_LAUNCH
+            if (!wide) {
+                switch (L) {
+                    case 1: DFX_TAPS(1, false); break;
+                    case 2: DFX_TAPS(2, false); break;
+                    case 3: DFX_TAPS(3, false); break;
+                    default: DFX_TAPS(4, false); break;
+                }
+            }
 #undef DFX_TAPS
             return dfx::check_launch(half ? "msda_half_fwd_taps" : "msda_fwd_taps");
         }
         if constexpr (!half) {
             if (fast) {
                 const int grid = (int)((nq + 3) / 4);
-                hipLaunchKernelGGL((msda_fwd_m8d32<0, true>), dim3(grid), dim3(256), 0, st, value, shapes, lsi,
+                hipLaunchKernelGGL(msda_fwd_m8d32, dim3(grid), dim3(256), 0, st, value, shapes, lsi,
                                    loc, aw, (int)nq, Lq, S, L, P, out);
                 return dfx::check_launch("msda_fwd_m8d32");
             }

@@ -132,7 +132,7 @@ __global__ __launch_bounds__(256) void msda_fused_taps(const float *__restrict__
             if (qi < NQ) {
                 const int b = qi / Lq;
                 const char *vb = reinterpret_cast<const char *>(value) + (size_t)b * S * 1024;
-                const float4 acc = dfx::gather_query<LT>(vb, lane_b, m, toff + qq * LT * 32, tw + qq * LT * 32);
+                const float4 acc = dfx::gather_query<LT, float>(vb, lane_b, m, toff + qq * LT * 32, tw + qq * LT * 32);
                 *reinterpret_cast<float4 *>(out + (long)qi * 256 + lane * 4) = acc;
             }
         }

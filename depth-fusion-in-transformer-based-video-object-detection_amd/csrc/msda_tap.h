@@ -9,7 +9,7 @@
 // gather phase as two conflict-free 16-byte broadcasts per point.
 //
 // Also the value-dtype helpers of the MSDA kernels (fp32, fp64, bf16, fp16): the arithmetic type of
-// a value dtype and the packed 2-byte channel loads / stores.
+// a value dtype and the packed channel loads / stores.
 #pragma once
 #include <hip/hip_bf16.h>
 
@@ -24,12 +24,13 @@ namespace dfx {
 template <typename V>
 using Acc = typename std::conditional<std::is_same<V, double>::value, double, float>::type;
 
-// K consecutive 2-byte channels, loaded / stored as one 2K-byte access
+// K consecutive channels of a value dtype T, loaded / stored as one access of K * sizeof(T) bytes
 template <typename T, int K>
-struct alignas(2 * K) Pack {
+struct alignas(sizeof(T) * K) Pack {
     T v[K];
 };
 
+// widen4 / narrow4: 4 channels to and from the fp32 the kernels compute in (the identity for T = float)
 template <typename T>
 __device__ __forceinline__ float4 widen4(const Pack<T, 4> &p)
 {
@@ -94,8 +95,7 @@ __device__ __forceinline__ Tap make_tap(float lx, float ly, float a, int H, int 
 // Phase A of the unfused wave-per-query forward (M = 8 heads, P = 4 points, LT levels): lane =
 // one (query, level, point, head) sample of the QW queries q0 .. q0+QW-1; it reads its (x, y)
 // pair and attention weight once and writes its tap to LDS slot ((qq*LT + l)*4 + p)*8 + head.
-// Queries at or past NQ get zero taps (offset 0, weight 0).  (msda_fwd_taps keeps the fp32 form of
-// this loop inline: routing it through here changes that kernel's instruction schedule.)
+// Queries at or past NQ get zero taps (offset 0, weight 0).
 template <int LT>
 struct LevelDims {
     int H[LT], W[LT], R[LT];     // (H_l, W_l, level_start_index[l]) of every level
@@ -150,10 +150,10 @@ __device__ __forceinline__ void wave_lds_fence()
 
 // Gather phase for ONE query: lane = (head m = lane&7 ... see callers), reads its head's taps of
 // every (level, point) from LDS and accumulates 4 channels.
-//   vb        : wave-uniform pointer to the batch element's value slab
-//   lane_b    : cg * 16 (byte offset of this lane's channel quad inside the head's 128 bytes)
+//   vb        : wave-uniform pointer to the batch element's value slab (value dtype V)
+//   lane_b    : cg * 4 * sizeof(V) (byte offset of this lane's channel quad inside the head's 32 channels)
 //   toff/tw   : LDS tap arrays of this query, [LT][4 points][8 heads]
-template <int LT>
+template <int LT, typename V>
 __device__ __forceinline__ float4 gather_query(const char *__restrict__ vb, unsigned lane_b, int m,
                                                const uint4 *toff, const float4 *tw)
 {
@@ -167,20 +167,20 @@ __device__ __forceinline__ float4 gather_query(const char *__restrict__ vb, unsi
             o[p] = toff[(l * 4 + p) * 8 + m];
             w[p] = tw[(l * 4 + p) * 8 + m];
         }
-        float4 v[16];
+        Pack<V, 4> v[16];
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
-            v[p * 4 + 0] = *reinterpret_cast<const float4 *>(vb + (o[p].x + lane_b));
-            v[p * 4 + 1] = *reinterpret_cast<const float4 *>(vb + (o[p].y + lane_b));
-            v[p * 4 + 2] = *reinterpret_cast<const float4 *>(vb + (o[p].z + lane_b));
-            v[p * 4 + 3] = *reinterpret_cast<const float4 *>(vb + (o[p].w + lane_b));
+            v[p * 4 + 0] = *reinterpret_cast<const Pack<V, 4> *>(vb + (o[p].x + lane_b));
+            v[p * 4 + 1] = *reinterpret_cast<const Pack<V, 4> *>(vb + (o[p].y + lane_b));
+            v[p * 4 + 2] = *reinterpret_cast<const Pack<V, 4> *>(vb + (o[p].z + lane_b));
+            v[p * 4 + 3] = *reinterpret_cast<const Pack<V, 4> *>(vb + (o[p].w + lane_b));
         }
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
-            fma4(acc, w[p].x, v[p * 4 + 0]);
-            fma4(acc, w[p].y, v[p * 4 + 1]);
-            fma4(acc, w[p].z, v[p * 4 + 2]);
-            fma4(acc, w[p].w, v[p * 4 + 3]);
+            fma4(acc, w[p].x, widen4<V>(v[p * 4 + 0]));
+            fma4(acc, w[p].y, widen4<V>(v[p * 4 + 1]));
+            fma4(acc, w[p].z, widen4<V>(v[p * 4 + 2]));
+            fma4(acc, w[p].w, widen4<V>(v[p * 4 + 3]));
         }
     }
     return acc;
