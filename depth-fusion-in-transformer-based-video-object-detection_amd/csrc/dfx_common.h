@@ -70,6 +70,7 @@ struct Tuning {
     bool level_variant_set = false;  // DFX_LEVEL_VARIANT given
     int level_variant = 0;           // DFX_LEVEL_VARIANT: kernel variant of msda_level.hip (A/B)
     bool msda_half_narrow = false;   // DFX_MSDA_HALF_NARROW: 8-byte (8 lanes per head) gather of the 2-byte msda_fwd_taps at L = 1 too (A/B)
+    bool roi_bwd_plain = false;      // DFX_ROI_BWD_PLAIN: the unmerged 4*sr^2-row RoIAlign backward (A/B)
     void read()
     {
         *this = Tuning();
@@ -89,6 +90,7 @@ struct Tuning {
         level_variant_set = flag("DFX_LEVEL_VARIANT");
         level_variant = num("DFX_LEVEL_VARIANT", 0);
         msda_half_narrow = flag("DFX_MSDA_HALF_NARROW");
+        roi_bwd_plain = flag("DFX_ROI_BWD_PLAIN");
     }
 };
 inline Tuning &tuning_slot()

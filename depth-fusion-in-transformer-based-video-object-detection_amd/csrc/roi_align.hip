@@ -9,6 +9,23 @@
 // the bin's output row leaves as one coalesced store.  The encoder memory is already token-major
 // ([H*W, C]), so the reference's permute+contiguous copy to NCHW (multi_plusplus.py:498,513)
 // disappears.  NCHW kernel: one thread per output element, for API parity with mmcv's layout.
+//
+// Backward = the transpose of that map, for the feature map only (RoIs get no gradient, as in mmcv's op):
+// grad_input[b, pixel] += grad_out[k, bin] * w / sr^2 for every corner of every valid sample, by the hardware
+// fp32 atomics the MSDA backward uses (unsafeAtomicAdd -> global_atomic_add_f32, no compare-and-swap loop).
+// Both directions go through load_roi / locate, so they take the same skip / clamp decision for every sample.
+//   roi_align_bwd_nhwc  one wave per (roi, bin) like the forward.  Lane l owns channels l, l + 64, ...: the bin's
+//     grad_out row is read as coalesced 256-byte segments and every atomic wave instruction adds 256 contiguous
+//     bytes of one pixel's channel row - the shape that runs at the chip-wide atomic rate.  A sample is valid when
+//     ok_y & ok_x and its corner weights are (hy | ly) x (hx | lx), so the bin's whole contribution is the outer
+//     product of a per-row weight vector (<= 2*sr entries) and a per-column one.  Both are built once per wave
+//     (the bin is the same for all 64 lanes) with equal indices merged and zero weights dropped, which takes the
+//     4*sr^2 pixel rows of the plain form (16 at sr = 2) down to 4..9 for bins narrower than two pixels.
+//   roi_align_bwd_nhwc_plain  the unmerged form, four adds per sample: sampling_ratio > 4 (the merge tables hold
+//     8 entries) and the A/B switch DFX_ROI_BWD_PLAIN.
+//   roi_align_bwd_nchw  API parity with the NCHW forward: one thread per grad_out element, four scalar atomics per
+//     sample, i.e. 64 lanes in 64 different rows per wave instruction - an order of magnitude below the shaped
+//     form's atomic rate.  The model never takes it (frame_stage hands RoIAlign a channels-last view).
 #include "dfx_common.h"
 #include "dfx_roi.h"
 
@@ -117,6 +134,126 @@ __global__ __launch_bounds__(256) void roi_align_nchw(const float *__restrict__ 
     }
 }
 
+// One axis of a bin's sampling grid: (index, weight) of every map row / column some valid sample touches, equal
+// indices merged, in the order met.  locate() with the other coordinate at 0 is always ok on that axis and gives
+// w1 = h, w3 / w2 = l exactly (its fraction there is 0), so the decisions are the forward's, bit for bit.
+template <int SR>
+struct AxisTaps {
+    int idx[2 * SR];
+    float w[2 * SR];
+    int n = 0;
+    __device__ __forceinline__ void add(int at, float wgt)
+    {
+        if (wgt == 0.f) return;
+        bool found = false;
+#pragma unroll
+        for (int t = 0; t < 2 * SR; ++t)
+            if (t < n && idx[t] == at) { w[t] += wgt; found = true; }
+        if (found) return;
+#pragma unroll
+        for (int t = 0; t < 2 * SR; ++t)
+            if (t == n) { idx[t] = at; w[t] = wgt; }
+        ++n;
+    }
+};
+
+template <int SR>
+__global__ __launch_bounds__(256) void roi_align_bwd_nhwc(const float *__restrict__ gout, const float *__restrict__ rois,
+                                                          int N, int C, int H, int W, long nbins, int ph, int pw,
+                                                          float scale, int aligned, float *__restrict__ gin)
+{
+    const long bin = (long)blockIdx.x * 4 + (threadIdx.x >> 6);     // one wave per (roi, bin)
+    if (bin >= nbins) return;
+    const int lane = threadIdx.x & 63;
+    const int k = (int)(bin / (ph * pw)), ij = (int)(bin % (ph * pw));
+    const int i = ij / pw, j = ij % pw;
+    const Roi r = load_roi(rois + 5 * (long)k, scale, aligned, ph, pw);
+    if (r.b < 0 || r.b >= N) return;
+    AxisTaps<SR> ty, tx;
+#pragma unroll
+    for (int s = 0; s < SR; ++s) {
+        const float y = r.y1 + i * r.bin_h + (s + 0.5f) * r.bin_h / (float)SR;
+        const Sample a = locate(y, 0.f, H, W);
+        if (a.ok) { ty.add(a.yl, a.w1); ty.add(a.yh, a.w3); }
+        const float x = r.x1 + j * r.bin_w + (s + 0.5f) * r.bin_w / (float)SR;
+        const Sample b = locate(0.f, x, H, W);
+        if (b.ok) { tx.add(b.xl, b.w1); tx.add(b.xh, b.w2); }
+    }
+    if (ty.n == 0 || tx.n == 0) return;
+    const float inv = 1.f / (float)(SR * SR);
+    float *dst = gin + (long)r.b * H * W * C;
+    const float *g = gout + bin * C;
+    for (int c = lane; c < C; c += 64) {
+        const float gv = g[c] * inv;
+#pragma unroll
+        for (int a = 0; a < 2 * SR; ++a) {
+            if (a >= ty.n) break;
+#pragma unroll
+            for (int b = 0; b < 2 * SR; ++b) {
+                if (b >= tx.n) break;
+                unsafeAtomicAdd(dst + ((long)ty.idx[a] * W + tx.idx[b]) * C + c, ty.w[a] * tx.w[b] * gv);
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void roi_align_bwd_nhwc_plain(const float *__restrict__ gout, const float *__restrict__ rois,
+                                                                int N, int C, int H, int W, long nbins, int ph, int pw,
+                                                                float scale, int sr, int aligned, float *__restrict__ gin)
+{
+    const long bin = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (bin >= nbins) return;
+    const int lane = threadIdx.x & 63;
+    const int k = (int)(bin / (ph * pw)), ij = (int)(bin % (ph * pw));
+    const int i = ij / pw, j = ij % pw;
+    const Roi r = load_roi(rois + 5 * (long)k, scale, aligned, ph, pw);
+    if (r.b < 0 || r.b >= N) return;
+    const float inv = 1.f / (float)(sr * sr);
+    float *dst = gin + (long)r.b * H * W * C;
+    const float *g = gout + bin * C;
+    for (int c = lane; c < C; c += 64) {
+        const float gv = g[c] * inv;
+        for (int iy = 0; iy < sr; ++iy) {
+            const float y = r.y1 + i * r.bin_h + (iy + 0.5f) * r.bin_h / (float)sr;
+            for (int ix = 0; ix < sr; ++ix) {
+                const float x = r.x1 + j * r.bin_w + (ix + 0.5f) * r.bin_w / (float)sr;
+                const Sample s = locate(y, x, H, W);
+                if (!s.ok) continue;
+                unsafeAtomicAdd(dst + ((long)s.yl * W + s.xl) * C + c, s.w1 * gv);
+                unsafeAtomicAdd(dst + ((long)s.yl * W + s.xh) * C + c, s.w2 * gv);
+                unsafeAtomicAdd(dst + ((long)s.yh * W + s.xl) * C + c, s.w3 * gv);
+                unsafeAtomicAdd(dst + ((long)s.yh * W + s.xh) * C + c, s.w4 * gv);
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void roi_align_bwd_nchw(const float *__restrict__ gout, const float *__restrict__ rois,
+                                                          int N, int C, int H, int W, long total, int ph, int pw,
+                                                          float scale, int sr, int aligned, float *__restrict__ gin)
+{
+    for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
+        const int j = (int)(idx % pw), i = (int)((idx / pw) % ph);
+        const int c = (int)((idx / ((long)pw * ph)) % C), k = (int)(idx / ((long)pw * ph * C));
+        const Roi r = load_roi(rois + 5 * (long)k, scale, aligned, ph, pw);
+        if (r.b < 0 || r.b >= N) continue;
+        float *dst = gin + ((long)r.b * C + c) * H * W;
+        const float gv = gout[idx] / (float)(sr * sr);
+        for (int iy = 0; iy < sr; ++iy) {
+            const float y = r.y1 + i * r.bin_h + (iy + 0.5f) * r.bin_h / (float)sr;
+            for (int ix = 0; ix < sr; ++ix) {
+                const float x = r.x1 + j * r.bin_w + (ix + 0.5f) * r.bin_w / (float)sr;
+                const Sample s = locate(y, x, H, W);
+                if (!s.ok) continue;
+                unsafeAtomicAdd(dst + s.yl * W + s.xl, s.w1 * gv);
+                unsafeAtomicAdd(dst + s.yl * W + s.xh, s.w2 * gv);
+                unsafeAtomicAdd(dst + s.yh * W + s.xl, s.w3 * gv);
+                unsafeAtomicAdd(dst + s.yh * W + s.xh, s.w4 * gv);
+            }
+        }
+    }
+}
+
 int check(const void *in, const void *rois, const void *out, int N, int C, int H, int W, int K, int ph, int pw, int sr)
 {
     if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || K < 0 || ph <= 0 || pw <= 0)
@@ -155,4 +292,65 @@ extern "C" int dfx_roi_align_nchw_f32(const float *input, const float *rois, int
     hipLaunchKernelGGL(roi_align_nchw, dim3(dfx::grid_for(total)), dim3(256), 0, static_cast<hipStream_t>(stream),
                        input, rois, N, C, H, W, total, ph, pw, spatial_scale, sampling_ratio, aligned, out);
     return dfx::check_launch("roi_align_nchw");
+}
+
+// ---- backward: grad_input is zero-filled here, on `stream`, then accumulated into ---------------------------
+namespace {
+
+// <0: error, 1: nothing to add (grad_input zero-filled), 0: zero-filled, go on
+int begin_backward(const float *grad_out, const float *rois, float *grad_input, int N, int C, int H, int W, int K,
+                   int ph, int pw, int sr, bool nhwc, hipStream_t st)
+{
+    if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || K < 0 || ph <= 0 || pw <= 0)
+        return dfx::fail(DFX_EINVAL, "roi_align_backward: bad dimension");
+    if (sr <= 0) return dfx::fail(DFX_EINVAL, "roi_align_backward: sampling_ratio must be > 0 (adaptive grids are not used on this path)");
+    if (!grad_input || (K > 0 && (!grad_out || !rois))) return dfx::fail(DFX_EINVAL, "roi_align_backward: null pointer");
+    if (nhwc && K > 0 && ((C & 3) || !dfx::aligned16(grad_out) || !dfx::aligned16(grad_input)))
+        return dfx::fail(DFX_EINVAL, "roi_align_backward nhwc: C %% 4 == 0 and 16-byte aligned buffers required");
+    const hipError_t e = hipMemsetAsync(grad_input, 0, (size_t)N * C * H * W * sizeof(float), st);
+    if (e != hipSuccess) return dfx::fail(DFX_ELAUNCH, "roi_align_backward: zero fill: %s", hipGetErrorString(e));
+    return K == 0 ? 1 : 0;
+}
+
+}  // namespace
+
+extern "C" int dfx_roi_align_backward_nhwc_f32(const float *grad_out, const float *rois, int N, int C, int H, int W, int K,
+                                               int ph, int pw, float spatial_scale, int sampling_ratio, int aligned,
+                                               float *grad_input, void *stream)
+{
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int rc = begin_backward(grad_out, rois, grad_input, N, C, H, W, K, ph, pw, sampling_ratio, true, st);
+    if (rc < 0) return rc;
+    if (rc == 1) return DFX_OK;
+    const long nbins = (long)K * ph * pw;
+    const dim3 grid((unsigned)((nbins + 3) / 4)), block(256);
+    const int sr = dfx::tuning().roi_bwd_plain ? 0 : sampling_ratio;
+#define DFX_ROI_BWD(SR)                                                                                                \
+    hipLaunchKernelGGL(roi_align_bwd_nhwc<SR>, grid, block, 0, st, grad_out, rois, N, C, H, W, nbins, ph, pw, spatial_scale, \
+                       aligned, grad_input)
+    switch (sr) {
+    case 1: DFX_ROI_BWD(1); break;
+    case 2: DFX_ROI_BWD(2); break;
+    case 3: DFX_ROI_BWD(3); break;
+    case 4: DFX_ROI_BWD(4); break;
+    default:
+        hipLaunchKernelGGL(roi_align_bwd_nhwc_plain, grid, block, 0, st, grad_out, rois, N, C, H, W, nbins, ph, pw,
+                           spatial_scale, sampling_ratio, aligned, grad_input);
+    }
+#undef DFX_ROI_BWD
+    return dfx::check_launch("roi_align_bwd_nhwc");
+}
+
+extern "C" int dfx_roi_align_backward_nchw_f32(const float *grad_out, const float *rois, int N, int C, int H, int W, int K,
+                                               int ph, int pw, float spatial_scale, int sampling_ratio, int aligned,
+                                               float *grad_input, void *stream)
+{
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int rc = begin_backward(grad_out, rois, grad_input, N, C, H, W, K, ph, pw, sampling_ratio, false, st);
+    if (rc < 0) return rc;
+    if (rc == 1) return DFX_OK;
+    const long total = (long)K * C * ph * pw;
+    hipLaunchKernelGGL(roi_align_bwd_nchw, dim3(dfx::grid_for(total)), dim3(256), 0, st, grad_out, rois, N, C, H, W, total,
+                       ph, pw, spatial_scale, sampling_ratio, aligned, grad_input);
+    return dfx::check_launch("roi_align_bwd_nchw");
 }

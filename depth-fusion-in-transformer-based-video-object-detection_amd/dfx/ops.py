@@ -265,16 +265,10 @@ def msda_level_forward(value_blk, reference_points, qproj_blk, N, H, W):
     return out
 
 
-def roi_align(inp, rois, output_size, spatial_scale, sampling_ratio, aligned=True, channels_last=False):
-    """RoIAlign (avg, fixed sampling grid) through include/dfx_roi.h.
-
-    channels_last=False: inp [N,C,H,W] contiguous -> [K,C,ph,pw]
-    channels_last=True : inp [N,H,W,C] contiguous -> [K,ph*pw,C]   (token-major memory, no transpose)
-    rois [K,5] = (batch index, x1, y1, x2, y2)
-    """
+def _roi_align_forward(inp, rois, output_size, spatial_scale, sampling_ratio, aligned, channels_last):
+    """The forward entry of include/dfx_roi.h on a float [K,5] contiguous `rois`; no autograd node."""
     lib = _lib.load()
     ph, pw = (output_size, output_size) if isinstance(output_size, int) else output_size
-    rois = rois.contiguous().float()
     _check_inputs([("input", inp), ("rois", rois)])
     _require(inp.dtype == torch.float32, "roi_align is implemented for float32")
     _require(rois.dim() == 2 and rois.shape[1] == 5, "rois must be [K,5]")
@@ -292,6 +286,71 @@ def roi_align(inp, rois, output_size, spatial_scale, sampling_ratio, aligned=Tru
                 int(sampling_ratio), int(bool(aligned)), out.data_ptr(), _stream(inp.device))
     _lib.check(rc, "roi_align")
     return out
+
+
+def roi_align_backward(grad_out, rois, input_shape, output_size, spatial_scale, sampling_ratio, aligned=True,
+                       channels_last=False):
+    """Gradient of roi_align with respect to its input (the RoIs get none) through include/dfx_roi.h.
+
+    channels_last=False: grad_out [K,C,ph,pw] contiguous -> [N,C,H,W] = input_shape
+    channels_last=True : grad_out [K,ph*pw,C] contiguous -> [N,H,W,C] = input_shape
+    The library zero-fills the fresh result and accumulates into it with fp32 atomics.
+    """
+    lib = _lib.load()
+    ph, pw = (output_size, output_size) if isinstance(output_size, int) else output_size
+    rois = rois.contiguous().float()
+    _check_inputs([("grad_output", grad_out), ("rois", rois)])
+    _require(grad_out.dtype == torch.float32, "roi_align_backward is implemented for float32")
+    _require(rois.dim() == 2 and rois.shape[1] == 5, "rois must be [K,5]")
+    _require(len(input_shape) == 4, "input_shape must be the forward input's 4-d shape")
+    K = rois.shape[0]
+    if channels_last:
+        N, H, W, C = input_shape
+        want, fn = (K, ph * pw, C), lib.dfx_roi_align_backward_nhwc_f32
+    else:
+        N, C, H, W = input_shape
+        want, fn = (K, C, ph, pw), lib.dfx_roi_align_backward_nchw_f32
+    _require(tuple(grad_out.shape) == want, f"grad_output must be {want}, got {tuple(grad_out.shape)}")
+    grad_input = torch.empty(tuple(input_shape), dtype=grad_out.dtype, device=grad_out.device)
+    with _on(grad_out.device):
+        rc = fn(grad_out.data_ptr(), rois.data_ptr(), N, C, H, W, K, ph, pw, float(spatial_scale),
+                int(sampling_ratio), int(bool(aligned)), grad_input.data_ptr(), _stream(grad_out.device))
+    _lib.check(rc, "roi_align_backward")
+    return grad_input
+
+
+class _RoIAlignFunction(torch.autograd.Function):
+    """apply(inp, rois, output_size, spatial_scale, sampling_ratio, aligned, channels_last); gradient for `inp` only."""
+
+    @staticmethod
+    def forward(ctx, inp, rois, output_size, spatial_scale, sampling_ratio, aligned, channels_last):
+        ctx.args = (tuple(inp.shape), output_size, spatial_scale, sampling_ratio, aligned, channels_last)
+        ctx.save_for_backward(rois)
+        return _roi_align_forward(inp, rois, output_size, spatial_scale, sampling_ratio, aligned, channels_last)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        rois, = ctx.saved_tensors
+        shape, output_size, spatial_scale, sampling_ratio, aligned, channels_last = ctx.args
+        grad_input = roi_align_backward(grad_output.contiguous(), rois, shape, output_size, spatial_scale, sampling_ratio,
+                                        aligned, channels_last)
+        return grad_input, None, None, None, None, None, None
+
+
+def roi_align(inp, rois, output_size, spatial_scale, sampling_ratio, aligned=True, channels_last=False):
+    """RoIAlign (avg, fixed sampling grid) through include/dfx_roi.h.
+
+    channels_last=False: inp [N,C,H,W] contiguous -> [K,C,ph,pw]
+    channels_last=True : inp [N,H,W,C] contiguous -> [K,ph*pw,C]   (token-major memory, no transpose)
+    rois [K,5] = (batch index, x1, y1, x2, y2)
+    With grad mode on and an input that requires a gradient the result carries it back into `inp`
+    (roi_align_backward); the RoIs get no gradient.  Otherwise no autograd node is made.
+    """
+    rois = rois.contiguous().float()
+    if inp.requires_grad and torch.is_grad_enabled():
+        return _RoIAlignFunction.apply(inp, rois, output_size, spatial_scale, sampling_ratio, aligned, channels_last)
+    return _roi_align_forward(inp, rois, output_size, spatial_scale, sampling_ratio, aligned, channels_last)
 
 
 def bias_act_(x, bias, residual=None, relu=True):

@@ -1,7 +1,12 @@
 """``RoIAlign`` module with the call surface of ``mmcv.ops.RoIAlign`` as the reference uses it
 (/root/reference/models/deformable_transformer_multi_plusplus.py:129-132:
 ``RoIAlign(output_size=7, spatial_scale=1/32, sampling_ratio=2)``; mmcv-1.7.0 defaults
-``pool_mode='avg'``, ``aligned=True``), on the gfx950 kernel behind include/dfx_roi.h.
+``pool_mode='avg'``, ``aligned=True``), on the gfx950 kernels behind include/dfx_roi.h.
+
+Like mmcv's op it is differentiable in the feature map only: with autograd recording and an input that requires a
+gradient, ``dfx.ops.roi_align`` goes through an autograd function whose backward is ``dfx_roi_align_backward_*``
+(every route below: NCHW, the channels-last view, ``forward_tokens``); the RoIs get no gradient.  Without recording
+no autograd node is made.
 """
 import torch
 from torch import nn

@@ -30,6 +30,21 @@ int dfx_roi_align_nhwc_f32(const float *input, const float *rois, int N, int C, 
                            int ph, int pw, float spatial_scale, int sampling_ratio, int aligned,
                            float *out, void *stream);
 
+/* Backward of the two entry points above: the transpose of the forward map, for the feature map only (the RoIs get
+ * no gradient, as in the published mmcv op).  grad_out has the forward's output layout, grad_input the forward's
+ * input layout.  Unlike dfx_msda_backward_* the entry point zero-fills grad_input [N*C*H*W floats] itself on
+ * `stream` before it accumulates into it with fp32 atomic adds (also when K == 0, where it then returns), so
+ * sums may differ in the last bits from run to run.  Samples the forward skips, and RoIs whose batch index is
+ * outside [0, N), contribute nothing.  Same argument rules as the forward; nhwc: C a multiple of 4, grad_out and
+ * grad_input 16-byte aligned.  Additions to the ABI: no existing signature changes, dfx_abi_version() stays. */
+int dfx_roi_align_backward_nchw_f32(const float *grad_out, const float *rois, int N, int C, int H, int W, int K,
+                                    int ph, int pw, float spatial_scale, int sampling_ratio, int aligned,
+                                    float *grad_input, void *stream);
+
+int dfx_roi_align_backward_nhwc_f32(const float *grad_out, const float *rois, int N, int C, int H, int W, int K,
+                                    int ph, int pw, float spatial_scale, int sampling_ratio, int aligned,
+                                    float *grad_input, void *stream);
+
 /* DynamicConv of the query/RoI fusion head (Sparse R-CNN instance interaction) between the parameter
  * Linear and the output Linear, one launch (/root/reference/models/sparse_roi_head/head.py:98-113):
  *   k1 = params[r, 0 : C*dd] as [C,dd];  k2 = params[r, C*dd : 2*C*dd] as [dd,C]
