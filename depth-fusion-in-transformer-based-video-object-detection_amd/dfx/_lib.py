@@ -37,6 +37,8 @@ SIGNATURES = {
     "dfx_roi_align_backward_nchw_f32": [_p, _p] + [_i] * 7 + [ctypes.c_float, _i, _i, _p, _p],
     "dfx_roi_align_backward_nhwc_f32": [_p, _p] + [_i] * 7 + [ctypes.c_float, _i, _i, _p, _p],
     "dfx_dynamic_conv_f32": [_p, _p, _l, _p, _p, _p, _p, _p, _i, _i, _i, _i, ctypes.c_float, _p],
+    # grad_out, feats, params, p_stride, g1, b1, g2, b2, grad_feats, grad_params, gp_stride, grad_ln, workspace, K, R, C, dd, eps
+    "dfx_dynamic_conv_backward_f32": [_p, _p, _p, _l, _p, _p, _p, _p, _p, _p, _l, _p, _p, _i, _i, _i, _i, ctypes.c_float, _p],
     # include/dfx_preprocess.h
     "dfx_preprocess_u8_f32": [_p, _i, _i, _i, _p, _p, _i, _p, _p, _i, _i, _i, _p, _p, _p, _l, _i, _i, _p, _p],
     # include/dfx_gemm.h

@@ -548,11 +548,7 @@ def conv1x1_pair(x1, x2, weight, bias=None, relu=False):
     return out
 
 
-def dynamic_conv(feats, params, norm1, norm2):
-    """relu(norm2(relu(norm1(feats @ k1)) @ k2)) per RoI with k1, k2 cut from ``params`` (include/dfx_roi.h,
-    dfx_dynamic_conv_f32): feats [K,R,256] contiguous, params [K, 2*256*64] (rows may be strided), norm1 / norm2
-    nn.LayerNorm(64) / nn.LayerNorm(256).  -> [K,R,256]"""
-    lib = _lib.load()
+def _dynamic_conv_checks(feats, params, norm1, norm2):
     _check_inputs([("feats", feats), ("norm1.weight", norm1.weight), ("norm2.weight", norm2.weight)])
     K, R, C = feats.shape
     dd = norm1.normalized_shape[0]
@@ -560,6 +556,13 @@ def dynamic_conv(feats, params, norm1, norm2):
              and params.shape[1] >= 2 * C * dd and params.dtype == torch.float32 and feats.dtype == torch.float32,
              "dynamic_conv: params must be [K, 2*C*dd] fp32 with contiguous rows")
     _require(norm2.normalized_shape[0] == C and norm1.eps == norm2.eps, "dynamic_conv: norm shapes / eps")
+    return K, R, C, dd
+
+
+def _dynamic_conv_forward(feats, params, norm1, norm2):
+    """The forward entry of include/dfx_roi.h (dfx_dynamic_conv_f32); no autograd node."""
+    lib = _lib.load()
+    K, R, C, dd = _dynamic_conv_checks(feats, params, norm1, norm2)
     out = torch.empty_like(feats)
     with _on(feats.device):
         rc = lib.dfx_dynamic_conv_f32(feats.data_ptr(), params.data_ptr(), params.stride(0), norm1.weight.data_ptr(),
@@ -567,6 +570,80 @@ def dynamic_conv(feats, params, norm1, norm2):
                                       out.data_ptr(), K, R, C, dd, float(norm1.eps), _stream(feats.device))
     _lib.check(rc, "dynamic_conv")
     return out
+
+
+DYNCONV_BWD_WS_FLOATS = 256 * 640      # DFX_DYNCONV_BWD_WS_FLOATS of include/dfx_roi.h
+
+
+def dynamic_conv_backward(grad_out, feats, params, norm1, norm2, need_feats=True, need_params=True):
+    """Gradients of dynamic_conv from its inputs alone (include/dfx_roi.h, dfx_dynamic_conv_backward_f32: the kernel
+    recomputes the intermediates).  grad_out [K,R,256] contiguous.
+    -> (grad_feats [K,R,256] | None, grad_params like params (zeros beyond column 2*C*dd) | None,
+        grad_norm1_weight, grad_norm1_bias, grad_norm2_weight, grad_norm2_bias)
+    No atomics: two calls on the same inputs give the same bits."""
+    lib = _lib.load()
+    K, R, C, dd = _dynamic_conv_checks(feats, params, norm1, norm2)
+    _check_inputs([("grad_out", grad_out)])
+    _require(grad_out.shape == feats.shape and grad_out.dtype == torch.float32 and grad_out.device == feats.device,
+             "dynamic_conv_backward: grad_out must match feats")
+    width = params.shape[1]
+    grad_feats = torch.empty_like(feats) if need_feats else None
+    grad_params = None
+    pitch = (width + 3) // 4 * 4          # the kernel wants rows that start 16-byte aligned; the result is a column slice
+    if need_params:       # the kernel writes columns 0 .. 2*C*dd of every row
+        grad_params = (torch.empty if width == 2 * C * dd else torch.zeros)((K, pitch), dtype=torch.float32, device=feats.device)
+    grad_ln = torch.empty(2 * dd + 2 * C, dtype=torch.float32, device=feats.device)
+    ws = torch.empty(DYNCONV_BWD_WS_FLOATS, dtype=torch.float32, device=feats.device)
+    with _on(feats.device):
+        rc = lib.dfx_dynamic_conv_backward_f32(
+            grad_out.data_ptr(), feats.data_ptr(), params.data_ptr(), params.stride(0), norm1.weight.data_ptr(),
+            norm1.bias.data_ptr(), norm2.weight.data_ptr(), norm2.bias.data_ptr(), _ptr(grad_feats), _ptr(grad_params), pitch,
+            grad_ln.data_ptr(), ws.data_ptr(), K, R, C, dd, float(norm1.eps), _stream(feats.device))
+    _lib.check(rc, "dynamic_conv_backward")
+    dg1, db1, dg2, db2 = grad_ln.split([dd, dd, C, C])
+    if grad_params is not None and pitch != width:
+        grad_params = grad_params[:, :width]
+    return grad_feats, grad_params, dg1, db1, dg2, db2
+
+
+class _NormView:
+    """What the entry points read of an nn.LayerNorm, over saved tensors."""
+
+    def __init__(self, weight, bias, eps):
+        self.weight, self.bias, self.eps, self.normalized_shape = weight, bias, eps, tuple(weight.shape)
+
+
+class _DynamicConvFunction(torch.autograd.Function):
+    """apply(feats, params, g1, b1, g2, b2, eps): saves its inputs only; the backward kernel recomputes the rest."""
+
+    @staticmethod
+    def forward(ctx, feats, params, g1, b1, g2, b2, eps):
+        ctx.eps = eps
+        ctx.save_for_backward(feats, params, g1, b1, g2, b2)
+        return _dynamic_conv_forward(feats, params, _NormView(g1, b1, eps), _NormView(g2, b2, eps))
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        feats, params, g1, b1, g2, b2 = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        gf, gp, dg1, db1, dg2, db2 = dynamic_conv_backward(grad_output.contiguous(), feats, params, _NormView(g1, b1, ctx.eps),
+                                                           _NormView(g2, b2, ctx.eps), need_feats=need[0], need_params=need[1])
+        return (gf, gp, dg1 if need[2] else None, db1 if need[3] else None, dg2 if need[4] else None,
+                db2 if need[5] else None, None)
+
+
+def dynamic_conv(feats, params, norm1, norm2):
+    """relu(norm2(relu(norm1(feats @ k1)) @ k2)) per RoI with k1, k2 cut from ``params`` (include/dfx_roi.h,
+    dfx_dynamic_conv_f32): feats [K,R,256] contiguous, params [K, 2*256*64] (rows may be strided), norm1 / norm2
+    nn.LayerNorm(64) / nn.LayerNorm(256).  -> [K,R,256]
+    With grad mode on and feats, params or a LayerNorm parameter requiring a gradient the result carries it back
+    through dynamic_conv_backward; otherwise no autograd node is made."""
+    if torch.is_grad_enabled() and (feats.requires_grad or params.requires_grad or norm1.weight.requires_grad
+                                    or norm1.bias.requires_grad or norm2.weight.requires_grad or norm2.bias.requires_grad):
+        _dynamic_conv_checks(feats, params, norm1, norm2)
+        return _DynamicConvFunction.apply(feats, params, norm1.weight, norm1.bias, norm2.weight, norm2.bias, float(norm1.eps))
+    return _dynamic_conv_forward(feats, params, norm1, norm2)
 
 
 def mha(q, k, v, heads, scale):

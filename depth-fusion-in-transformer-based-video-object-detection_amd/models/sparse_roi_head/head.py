@@ -7,6 +7,7 @@ with each query's 7x7 RoI feature, FFN.  ``DynamicConv`` (:127-172): every query
 to 256.
 """
 import math
+import os
 
 import torch
 import torch.nn.functional as F
@@ -16,6 +17,19 @@ from models.fused import Linear
 from models.transformer_layers import _linear_norm_add, _norm_add
 
 _DEFAULT_SCALE_CLAMP = math.log(100000.0 / 16)
+# DynamicConv in grad mode on the fused forward + fused backward (csrc/dynconv_backward.hip); DFX_DYNCONV_TRAIN=0 keeps the
+# library route (bmm + LayerNorm + ReLU under autograd) for A/B runs.  Read once at import.
+DYNCONV_TRAIN = os.environ.get("DFX_DYNCONV_TRAIN", "1") != "0"
+
+
+def _has_hooks(module):
+    """True when calling ``module`` would run a forward, forward-pre or backward hook: one registered on the module or a
+    global one (torch.nn.modules.module.register_module_*_hook), which runs for every module."""
+    from torch.nn.modules import module as _m
+    own = (module._forward_hooks, module._forward_pre_hooks, module._backward_hooks, getattr(module, "_backward_pre_hooks", None))
+    shared = (getattr(_m, name, None) for name in ("_global_forward_hooks", "_global_forward_pre_hooks", "_global_backward_hooks",
+                                                   "_global_backward_pre_hooks"))
+    return any(bool(h) for h in own) or any(bool(h) for h in shared)
 
 
 def _get_activation_fn(activation):
@@ -39,15 +53,24 @@ class DynamicConv(nn.Module):
         self.out_layer = Linear(self.hidden_dim * res ** 2, self.hidden_dim)
         self.norm3 = nn.LayerNorm(self.hidden_dim)
 
+    def _fused_route(self, feats):
+        """csrc/dynconv.hip (and, in grad mode, csrc/dynconv_backward.hip behind dfx.ops.dynamic_conv) serves this call.
+        The fused route never calls norm1, norm2 or activation, so in grad mode a hook on one of them selects the
+        unfused route (under no_grad hooks are ignored, as they always were)."""
+        if not (feats.is_cuda and feats.dtype == torch.float32 and feats.is_contiguous() and self.hidden_dim == 256
+                and self.dim_dynamic == 64 and feats.shape[1] <= 64 and isinstance(self.activation, nn.ReLU)):
+            return False
+        if not torch.is_grad_enabled():
+            return True
+        return DYNCONV_TRAIN and not (_has_hooks(self.norm1) or _has_hooks(self.norm2) or _has_hooks(self.activation))
+
     def forward(self, pro_features, roi_features, params=None):
         """pro_features (1, K, C); roi_features (49, K, C) -> (K, C).  ``params``: the output of ``dynamic_layer(pro_features)``
         when the caller already has it (it depends on the queries only: RCNNHead shares it between RoI feature sets)."""
         feats = roi_features.permute(1, 0, 2)                               # K,49,C
         if params is None:
             params = self.dynamic_layer(pro_features)
-        if (feats.is_cuda and feats.dtype == torch.float32 and not torch.is_grad_enabled() and feats.is_contiguous()
-                and self.hidden_dim == 256 and self.dim_dynamic == 64 and feats.shape[1] <= 64
-                and isinstance(self.activation, nn.ReLU)):
+        if self._fused_route(feats):
             # both per-RoI products and their LayerNorm + ReLU in one launch (csrc/dynconv.hip)
             from dfx import ops as _ops
             params2 = params.view(feats.shape[0], -1)                                       # K, 2*C*dd

@@ -57,6 +57,23 @@ int dfx_dynamic_conv_f32(const float *feats, const float *params, long p_stride,
                          const float *g1, const float *b1, const float *g2, const float *b2,
                          float *out, int K, int R, int C, int dd, float eps, void *stream);
 
+/* Backward of dfx_dynamic_conv_f32 from its inputs alone: the kernel recomputes the forward's intermediates per RoI
+ * (csrc/dynconv_backward.hip), nothing is saved between the two calls.  grad_out [K,R,C] is the gradient of `out`.
+ *   grad_feats  [K,R,C]           gradient of feats; null: not computed (its product and stores are skipped)
+ *   grad_params [K, >= 2*C*dd]    row stride gp_stride; columns 0 .. 2*C*dd of every row are written (dK1 then dK2),
+ *                                 columns beyond are not touched; null: not computed
+ *   grad_ln     [2*dd + 2*C]      dg1[dd] db1[dd] dg2[C] db2[C], summed over all K*R rows, always written
+ *   workspace   DFX_DYNCONV_BWD_WS_FLOATS floats, caller-owned, contents irrelevant before and after the call
+ * No atomics: every workgroup sums its own LayerNorm parameter gradients into one workspace row and a second kernel
+ * adds the rows in order, so for given K the results are bit-identical from run to run.  Same argument rules and
+ * geometry as the forward (C = 256, dd = 64, R <= 64, 16-byte aligned buffers, strides multiples of 4);  K == 0
+ * zero-fills grad_ln and returns.  An addition to the ABI: dfx_abi_version() stays. */
+#define DFX_DYNCONV_BWD_WS_FLOATS (256 * 640)
+int dfx_dynamic_conv_backward_f32(const float *grad_out, const float *feats, const float *params, long p_stride,
+                                  const float *g1, const float *b1, const float *g2, const float *b2,
+                                  float *grad_feats, float *grad_params, long gp_stride, float *grad_ln,
+                                  float *workspace, int K, int R, int C, int dd, float eps, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
