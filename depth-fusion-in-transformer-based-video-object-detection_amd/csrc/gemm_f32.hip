@@ -53,14 +53,11 @@ struct Args {
     const float *B2;      // two-segment [K,N] operand: rows k >= K1 come from B2 (row k - K1), same ldb; LDS-DMA path only
     long strideB2;
     int K1;
-    const float *ln_g, *ln_b;   // LayerNorm over the N columns after the epilogue's bias / activation / residual (N == BN == 256)
-    float ln_eps;
-    int act_first;        // the activation applies before the residual is added (y = LN(R + act(A x B + bias)))
     int group_m;          // tile order (placement only, never results): 0 = n fastest, then m, then z, as dispatched;
                           // > 0: workgroup ids are XCD-remapped (each XCD walks one contiguous range) and run m fastest inside
                           // groups of group_m tile rows, then along the columns of every batch element
     int fast_cblk;        // column-block-major C through the same LDS round trip (set by launch())
-    int fast_epi;         // wide epilogue in its lean form (set by launch(): no LayerNorm / GELU / act_first, C and R slices < 2 GiB)
+    int fast_epi;         // wide epilogue in its lean form (set by launch(): no GELU, C and R slices < 2 GiB)
     long strideBias;      // elements the column bias advances per batch element (wide column blocks run as a batch: dfx_gemm_f32)
 };
 
@@ -75,7 +72,7 @@ __device__ __forceinline__ float activate(float v, int act)      // 1: ReLU, 2: 
 // 2-3x the registers, i.e. a third of the resident waves)
 constexpr int min_blocks(int BM, int BN, int NW, int BK)
 {
-    return BK != 16 ? 1 : NW == 8 ? 4 : BM == 64 && BN == 256 ? 3 : BM == 128 && BN == 128 ? 3 : BM == 64 && BN == 128 ? 4
+    return BK != 16 ? 1 : NW == 8 ? 4 : BM == 128 && BN == 128 ? 3 : BM == 64 && BN == 128 ? 4
            : BM == 128 && BN == 64 ? 5 : BM == 64 && BN == 64 ? 6 : BM == 128 && BN == 96 ? 3 : BM == 128 && BN == 32 ? 6 : 1;
 }
 
@@ -94,7 +91,7 @@ __global__ __launch_bounds__(64 * WM * WN, min_blocks(BM, BN, WM * WN, BK)) void
     static_assert(BK % 8 == 0, "a ds_read_b128 covers 8 consecutive k (4 per lane half)");
     // one LDS object: the two operand stages, re-used by the epilogue as a [64][BN + 4] transpose buffer
     constexpr int A_SZ = BM * LDK, B_SZ = B_KN ? BK * LDB : BN * LDK;               // floats per stage
-    constexpr int PR = BN >= 256 ? 32 : 64;           // tile rows per epilogue pass through LDS
+    constexpr int PR = 64;                            // tile rows per epilogue pass through LDS
     constexpr int LDC = BN + 4, C_SZ = PR * LDC;
     constexpr int S_SZ = 2 * (A_SZ + B_SZ) > C_SZ ? 2 * (A_SZ + B_SZ) : C_SZ;
     __shared__ __attribute__((aligned(16))) float smem[S_SZ];
@@ -385,9 +382,6 @@ __global__ __launch_bounds__(64 * WM * WN, min_blocks(BM, BN, WM * WN, BK)) void
     }
 
     // ---- epilogue ----
-#if defined(DFX_GEMM_ABLATE_EPILOGUE)          // timing ablation (tools/r03_exp14.sh): one store per lane keeps the K loop alive
-    if (g.M > 0) { g.C[(long)blockIdx.x * NTHR + tid] = acc[0][0][0] + acc[MT - 1][NT - 1][15]; return; }
-#endif
     float *C = g.C + cz * g.strideC;
     const float *R = g.R ? g.R + bz * g.strideR : nullptr;
     const unsigned char *mask = g.mask ? g.mask + bz * g.strideMask : nullptr;
@@ -396,7 +390,7 @@ __global__ __launch_bounds__(64 * WM * WN, min_blocks(BM, BN, WM * WN, BK)) void
     constexpr int CQ = BN / 4;                                 // float4 per tile row
     if constexpr (NTHR % CQ == 0) if (g.wide_epilogue && g.fast_epi) {
         // The lean form of the wide epilogue below (same LDS round trip, same float4 rows).  An ablation that ends the tile
-        // after the K loop (tools/r03_exp14.sh, profiles/r03_gemm_epilogue_ablation.txt) showed the epilogue costing 13-16 % of
+        // after the K loop (profiles/r03_gemm_epilogue_ablation.txt) showed the epilogue costing 13-16 % of
         // a K = 256 launch and 4-5 % of a K = 1024 one - its vector instructions take issue slots from the other resident
         // workgroups' MFMAs - so it is cut to the instructions it needs:
         //   every wave writes one 32-row tile per pass (was: half of the waves two tiles, the others idle);
@@ -541,7 +535,6 @@ __global__ __launch_bounds__(64 * WM * WN, min_blocks(BM, BN, WM * WN, BK)) void
         // quarter of the memory instructions.  The convolutions with many output channels and a short K
         // (Bottleneck.conv3 + residual) are bound by exactly this traffic.
         float *Ct = smem;
-        const bool ln = BN == 256 && g.ln_g != nullptr;       // (a wave-instruction of the float4 loop covers one whole row)
 #pragma unroll
         for (int p = 0; p < BM / PR; ++p) {
             if (p > 0) __syncthreads();
@@ -567,25 +560,9 @@ __global__ __launch_bounds__(64 * WM * WN, min_blocks(BM, BN, WM * WN, BK)) void
                 float4 v = *reinterpret_cast<const float4 *>(&Ct[row * LDC + c4 * 4]);
                 if (brow) { const float b = biasp[m]; v.x += b; v.y += b; v.z += b; v.w += b; }
                 if (bcol) { const float4 b = *reinterpret_cast<const float4 *>(biasp + n); v.x += b.x; v.y += b.y; v.z += b.z; v.w += b.w; }
-                if (g.relu && g.act_first) { v.x = activate(v.x, g.relu); v.y = activate(v.y, g.relu); v.z = activate(v.z, g.relu); v.w = activate(v.w, g.relu); }
                 if (PREFETCH_R && use_rpre) { const f32x4 q = rpre[PREFETCH_R ? f0 / 256 : 0]; v.x += q[0]; v.y += q[1]; v.z += q[2]; v.w += q[3]; }
                 else if (R) { const float4 q = *reinterpret_cast<const float4 *>(R + (long)m * g.ldr + n); v.x += q.x; v.y += q.y; v.z += q.z; v.w += q.w; }
-                if (g.relu && !g.act_first) { v.x = activate(v.x, g.relu); v.y = activate(v.y, g.relu); v.z = activate(v.z, g.relu); v.w = activate(v.w, g.relu); }
-                if (ln) {
-                    // LayerNorm of the row the wave holds (64 lanes x 4 columns): mean, then the centred second moment
-                    float sum = (v.x + v.y) + (v.z + v.w);
-#pragma unroll
-                    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
-                    const float mean = sum * (1.f / 256.f);
-                    v.x -= mean; v.y -= mean; v.z -= mean; v.w -= mean;
-                    float sq = (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
-#pragma unroll
-                    for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o);
-                    const float rstd = 1.f / sqrtf(sq * (1.f / 256.f) + g.ln_eps);
-                    const float4 gm = *reinterpret_cast<const float4 *>(g.ln_g + n), bt = *reinterpret_cast<const float4 *>(g.ln_b + n);
-                    v.x = v.x * rstd * gm.x + bt.x; v.y = v.y * rstd * gm.y + bt.y;
-                    v.z = v.z * rstd * gm.z + bt.z; v.w = v.w * rstd * gm.w + bt.w;
-                }
+                if (g.relu) { v.x = activate(v.x, g.relu); v.y = activate(v.y, g.relu); v.z = activate(v.z, g.relu); v.w = activate(v.w, g.relu); }
                 if (mask && mask[m]) v = make_float4(0.f, 0.f, 0.f, 0.f);
                 *reinterpret_cast<float4 *>(C + (long)m * g.ldc + n) = v;
             }
@@ -623,15 +600,10 @@ __global__ __launch_bounds__(64 * WM * WN, min_blocks(BM, BN, WM * WN, BK)) void
     }
 }
 
-// Tile order of a launch (Args::group_m): every XCD walks one contiguous range of tiles, 8 tile rows at a time with the
-// row fastest, so that the workgroups resident on an XCD share few operand panels in its 4 MiB L2.  Measured at 32 frames
+// Tile order of a launch (Args::group_m, read from DFX_GEMM_GROUP): every XCD walks one contiguous range of tiles, 8 tile rows at
+// a time with the row fastest, so that the workgroups resident on an XCD share few operand panels in its 4 MiB L2.  Measured at 32 frames
 // (tools/bench_gemm.py, DFX_GEMM_GROUP = 0 / 1 / 2 / 4 / 8 / 16 / all rows in one process each, profiles/r03_gemm_order.txt):
 // 4 and 8 tie, 2.7 % less time over the path's shapes than the dispatch order (layer4 shortcut 4 %, layer2 conv3 6 %).
-int tile_group(const Args &g, int batch)
-{
-    return dfx::tuning().gemm_group;
-}
-
 template <int BM, int BN, int WM, int WN, int BK = 16>
 int launch(const Args &g_in, int batch, int b_is_kn, hipStream_t st)
 {
@@ -640,13 +612,13 @@ int launch(const Args &g_in, int batch, int b_is_kn, hipStream_t st)
     g.ny = (g.M + BM - 1) / BM;
     const long total = (long)g.nx * g.ny * batch * (g.splits > 1 ? g.splits : 1);
     if (total >= (1L << 31)) return dfx::fail(DFX_ERANGE, "gemm: too many tiles");
-    g.group_m = tile_group(g, batch);
-    g.fast_cblk = g.cblk > 0 && g.cblk % 4 == 0 && BN % g.cblk == 0 && g.N % g.cblk == 0 && !g.R && g.relu != 2 && !g.ln_g &&
+    g.group_m = dfx::tuning().gemm_group;
+    g.fast_cblk = g.cblk > 0 && g.cblk % 4 == 0 && BN % g.cblk == 0 && g.N % g.cblk == 0 && !g.R && g.relu != 2 &&
                   (!g.bias || g.bias_per_row || dfx::aligned16(g.bias)) && dfx::aligned16(g.C) && (g.cblk_stride & 3) == 0 && (g.strideC & 3) == 0 &&
-                  ((long)(g.N / g.cblk) * g.cblk_stride) * 4 < (1L << 31) && !dfx::tuning().gemm_old_epilogue;
+                  ((long)(g.N / g.cblk) * g.cblk_stride) * 4 < (1L << 31);
     // (row offsets of a tile reach up to BM rows past M before the hardware range check drops them: they must not wrap)
-    g.fast_epi = g.wide_epilogue && !g.ln_g && !g.act_first && g.relu != 2 && ((long)(g.M + BM) * g.ldc + g.N) * 4 < (1L << 31) &&
-                 (!g.R || ((long)(g.M + BM) * g.ldr + g.N) * 4 < (1L << 31)) && !dfx::tuning().gemm_old_epilogue;
+    g.fast_epi = g.wide_epilogue && g.relu != 2 && ((long)(g.M + BM) * g.ldc + g.N) * 4 < (1L << 31) &&
+                 (!g.R || ((long)(g.M + BM) * g.ldr + g.N) * 4 < (1L << 31));
     const dim3 grid((unsigned)total), block(64 * WM * WN);
     // measurement aid (dfx_profile_*): flops of the launch in the byte field, tag_a = -1 ([K,N] operand: 1x1 convolution)
     // or -2 (Linear), tag_b = tile
@@ -755,7 +727,7 @@ bool rows_kernel_applies(const Args &g, int batch, int b_is_kn)
 {
     const int max_rows = dfx::tuning().gemm_rows_max;          // tuning aid: the row limit (0 = kernel off)
     const int tiles_n = (g.N + 31) / 32;
-    return !b_is_kn && batch == 1 && g.splits <= 1 && !g.mask && !g.cblk && !g.ablk_stride && !g.B2 && !g.ln_g &&
+    return !b_is_kn && batch == 1 && g.splits <= 1 && !g.mask && !g.cblk && !g.ablk_stride && !g.B2 &&
            !g.bias_per_row && (g.M <= max_rows || (max_rows > 0 && g.N <= 128)) && (g.N <= 32 || (g.N % 32 == 0 && g.wide_epilogue)) && g.N <= 1024 &&
            (g.K == 256 || g.K == 512 || g.K == 1024) && (long)((g.M + 31) / 32) * tiles_n <= 9600;
 }
@@ -815,38 +787,10 @@ extern "C" int dfx_gemm_f32(const float *A, const float *A2, long lda, long stri
     }
     const int wide = c_block == 0 && (N & 3) == 0 && (ldc & 3) == 0 && (strideC & 3) == 0 && dfx::aligned16(C) &&
                      (!R || ((ldr & 3) == 0 && (strideR & 3) == 0 && dfx::aligned16(R))) &&
-                     (!bias || bias_per_row || dfx::aligned16(bias)) && !dfx::tuning().gemm_narrow_epilogue;
+                     (!bias || bias_per_row || dfx::aligned16(bias));
     Args g{A, A2, lda, strideA, B, ldb, strideB, bias, bias_per_row, R, ldr, strideR, row_mask, strideMask, C, ldc, strideC,
            M, N, K, relu, c_block, c_block_stride, a_block_stride, wide, 1, K};
     return choose_and_launch(g, batch, b_is_kn, static_cast<hipStream_t>(stream));
-}
-
-// C = LayerNorm(R + act(A x B^T + bias)) (or act after the residual) over rows of exactly 256 columns, in ONE launch: the
-// Linear that ends a transformer sub-block with its residual add and LayerNorm (include/dfx_gemm.h)
-extern "C" int dfx_linear_ln_f32(const float *A, const float *A2, long lda, long a_block_stride, const float *W, long ldw,
-                                 const float *bias, const float *R, long ldr, const float *gamma, const float *beta,
-                                 float eps, float *C, long ldc, int M, int K, int act, int act_first, void *stream)
-{
-    const int N = 256;
-    if (M < 0 || K <= 0) return dfx::fail(DFX_EINVAL, "linear_ln: bad dimension");
-    if (act < 0 || act > 2) return dfx::fail(DFX_EINVAL, "linear_ln: activation code must be 0, 1 or 2");
-    if (M == 0) return DFX_OK;
-    if (!A || !W || !C || !gamma || !beta) return dfx::fail(DFX_EINVAL, "linear_ln: null pointer");
-    if ((K & 3) || (lda & 3) || (ldw & 3) || (ldc & 3) || (ldr & 3) || !dfx::aligned16(A) || !dfx::aligned16(W) || !dfx::aligned16(C) ||
-        (A2 && !dfx::aligned16(A2)) || (R && !dfx::aligned16(R)) || (bias && !dfx::aligned16(bias)) || !dfx::aligned16(gamma) ||
-        !dfx::aligned16(beta))
-        return dfx::fail(DFX_EINVAL, "linear_ln: K and the leading dimensions must be multiples of 4, buffers 16-byte aligned");
-    if (a_block_stride < 0 || (a_block_stride > 0 && (a_block_stride < (long)M * 4 || (a_block_stride & 3) || A2)))
-        return dfx::fail(DFX_EINVAL, "linear_ln: K-block-major A needs a_block_stride >= 4 * M (a multiple of 4) and no A2");
-    const long ea = a_block_stride > 0 ? (long)(K / 4) * a_block_stride : (long)M * lda;
-    if (ea * 4 >= (1L << 31) || (long)N * ldw * 4 >= (1L << 31) || (R && (long)M * ldr * 4 >= (1L << 31)))
-        return dfx::fail(DFX_ERANGE, "linear_ln: an operand exceeds 2 GiB");
-    Args g{A, A2, lda, 0, W, ldw, 0, bias, 0, R, ldr, 0, nullptr, 0, C, ldc, 0, M, N, K, act, 0, 0, a_block_stride, 1, 1, K};
-    g.ln_g = gamma;
-    g.ln_b = beta;
-    g.ln_eps = eps;
-    g.act_first = act_first;
-    return launch<64, 256, 1, 4>(g, 1, 0, static_cast<hipStream_t>(stream));
 }
 
 // Y[n] = act(W x [X1[n]; X2[n]] + bias): the last 1x1 convolution of a bottleneck and its stride-1 projection shortcut in
@@ -881,16 +825,14 @@ int choose_and_launch(const Args &g, int batch, int b_is_kn, hipStream_t st)
     const long zb = (long)batch * (g.splits > 1 ? g.splits : 1);
     if (rows_kernel_applies(g, batch, b_is_kn)) return launch_rows(g, st);
     // tile choice.  Small M / N pick the matching narrow tile.
-    if (dfx::tuning().gemm_tile >= 0) {      // tuning aid: 0 = 128x128, 1 = 128x64, 2 = 64x128
-        const char force[1] = {(char)('0' + dfx::tuning().gemm_tile)};
-        if (force[0] == '0') return launch<128, 128, 2, 2>(g, batch, b_is_kn, st);
-        if (force[0] == '1') return launch<128, 64, 2, 2>(g, batch, b_is_kn, st);
-        if (force[0] == '2') return launch<64, 128, 1, 4>(g, batch, b_is_kn, st);
-        if (force[0] == '3') return launch<64, 128, 1, 4, 32>(g, batch, b_is_kn, st);
-        if (force[0] == '4') return launch<128, 128, 2, 2, 32>(g, batch, b_is_kn, st);
-        if (force[0] == '5') return launch<64, 64, 2, 2>(g, batch, b_is_kn, st);
-        if (force[0] == '6') return launch<64, 64, 2, 2, 64>(g, batch, b_is_kn, st);
-        if (force[0] == '7') return launch<256, 128, 4, 2>(g, batch, b_is_kn, st);
+    switch (dfx::tuning().gemm_tile) {       // tuning aid (DFX_GEMM_TILE): force one tile for every launch
+    case 0: return launch<128, 128, 2, 2>(g, batch, b_is_kn, st);
+    case 1: return launch<128, 64, 2, 2>(g, batch, b_is_kn, st);
+    case 2: return launch<64, 128, 1, 4>(g, batch, b_is_kn, st);
+    case 5: return launch<64, 64, 2, 2>(g, batch, b_is_kn, st);
+    case 6: return launch<64, 64, 2, 2, 64>(g, batch, b_is_kn, st);
+    case 7: return launch<256, 128, 4, 2>(g, batch, b_is_kn, st);
+    default: break;
     }
     if (M <= 64) return launch<64, 128, 1, 4>(g, batch, b_is_kn, st);
     if (N <= 32) return launch<128, 32, 4, 1>(g, batch, b_is_kn, st);
@@ -929,7 +871,7 @@ int choose_and_launch(const Args &g, int batch, int b_is_kn, hipStream_t st)
     // At most one 64 x 64 workgroup per CU (the 300-query layers of a small rank block: M = 1200, N = 256): nothing hides
     // the global-load latency of a K-step but the step before it, so the K loop runs at ~1 us per step whatever its
     // depth; 64-deep steps quarter their number (profiles/r02_rank_step.txt).
-    if (t64 <= 320 && K >= 128 && !dfx::tuning().gemm_no_deep) return launch<64, 64, 2, 2, 64>(g, batch, b_is_kn, st);
+    if (t64 <= 320 && K >= 128) return launch<64, 64, 2, 2, 64>(g, batch, b_is_kn, st);
     // deep 1x1 convolutions of an 8-frame block (layer4 conv1 2048 -> 512, layer2 conv1 512 -> 128): 128 x 64 once it gives
     // every CU 8 tiles, 4-5 % ahead of 64 x 64 / 64 x 128 there (profiles/r03_gemm_tiles_F4_F8.txt)
     if (b_is_kn && M % 128 == 0 && K >= 512 && g.splits <= 1 && (long)(M / 128) * ((N + 63) / 64) * zb >= 2048)

@@ -371,7 +371,7 @@ extern "C" int dfx_msda_forward_f16(const uint16_t *value, const int64_t *shapes
                                   Lq, P, reinterpret_cast<_Float16 *>(out), stream);
 }
 
-extern "C" int dfx_abi_version(void) { return 4; }
+extern "C" int dfx_abi_version(void) { return 5; }
 
 extern "C" int dfx_profile_enable(int on)
 {

@@ -378,18 +378,7 @@ def _ptr(t):
 
 
 _GEMM_MAX_BYTES = 1 << 31          # tests lower it to exercise the row-range path on small tensors
-# LayerNorm in the GEMM epilogue (dfx_linear_ln_f32) - OFF: measured slower than GEMM + add_layernorm on this chip (round 3,
-# profiles/r03_linear_ln.txt: the 64 x 256 tile that owns whole rows runs its K loop with 36 % more LDS-DMA pieces per MFMA than
-# the 128 x 128 tile and leaves 19 workgroups for the 1200-row Linears of a 4-frame block: spatial stage 16.80 -> 16.97 ms with
-# it on the 134 400-row Linears only, 16.7 -> 17.3 ms on all of them, the 4-frame rank step 16.65 -> 18.9 ms).  DFX_LINEAR_LN=1
-# turns it on for A/B runs; the callers' ``norm=`` plumbing then costs nothing when it is off.
-# (A/B of round 3: the residual in the GEMM epilogue instead of in the LayerNorm pass moves 0.06 ms of 15.5 in the spatial stage -
-# inside the noise; off)
-_RESIDUAL_IN_GEMM = os.environ.get("DFX_LN_RESIDUAL_IN_GEMM", "0") == "1"
-_FUSE_LN = os.environ.get("DFX_LINEAR_LN", "0") == "1"
-_FUSE_LN_MIN_ROWS = int(os.environ.get("DFX_LINEAR_LN_MIN_ROWS", "32768"))
-
-
+# (linear(norm=...) is the GEMM followed by add_layernorm: LayerNorm in the GEMM epilogue was measured slower, DESIGN.md "Residual + LayerNorm in the epilogue")
 _SPLITK_MIN_K = int(os.environ.get("DFX_SPLITK_MIN_K", "2048"))      # (A/B aids)
 _SPLITK_RANGE = int(os.environ.get("DFX_SPLITK_RANGE", "512"))
 
@@ -417,7 +406,7 @@ def linear(x, weight, bias=None, relu=False, residual=None, add=None, row_mask=N
     neighbours fused: the ``src + pos`` query add, the bias, ReLU, the residual add and
     value_proj's masked_fill.  x [..., K] contiguous, weight [N, K] -> [..., N].
 
-    norm: an nn.LayerNorm(256) applied to the result rows in the same launch (include/dfx_gemm.h, dfx_linear_ln_f32):
+    norm: an nn.LayerNorm(256) applied to the result rows by an add_layernorm launch after the GEMM:
     y = norm(residual + act(...)) with ``act_first`` (the activation before the residual add), else norm(act(... + residual));
     needs N == 256, no row_mask, no col_block.
 
@@ -456,25 +445,16 @@ def linear(x, weight, bias=None, relu=False, residual=None, add=None, row_mask=N
         _require(row_mask.numel() == M, "row_mask must have one entry per row")
         row_mask = row_mask.reshape(-1).to(torch.uint8) if row_mask.dtype != torch.uint8 else row_mask.reshape(-1)
     code = ACT[act] if act is not None else int(bool(relu))
-    if norm is not None:      # one contract for both routes below (separate LayerNorm pass / LayerNorm in the GEMM epilogue)
+    if norm is not None:
         _require(N == 256 and row_mask is None and not col_block and norm.weight.numel() == 256 and norm.weight.is_cuda,
                  "linear(norm=...): a LayerNorm over exactly 256 output columns, no row_mask / col_block")
-    if norm is not None and (not _FUSE_LN or M < _FUSE_LN_MIN_ROWS):       # the LayerNorm as its own pass
-        if (code and not act_first) or (not code and _RESIDUAL_IN_GEMM):
+        if code and not act_first:
             # the residual rides in the GEMM's epilogue (prefetched while the tile crosses LDS): the LayerNorm pass then reads one
             # tensor instead of two.  Same sum, same order: (x W^T + b) + residual
             y = linear(x, weight, bias, residual=residual, add=add, x_blocked=x_blocked, act=act, relu=relu)
             return add_layernorm(y, None, norm)
         y = linear(x, weight, bias, add=add, x_blocked=x_blocked, act=act, relu=relu)
         return add_layernorm(y, None if residual is None else residual.reshape(y.shape), norm)
-    if norm is not None:
-        _require(M * K * 4 < _GEMM_MAX_BYTES, "linear(norm=...): operand of 2 GiB or more")
-        with _on(x.device):
-            rc = lib.dfx_linear_ln_f32(x2.data_ptr(), _ptr(add), K, M * 4 if x_blocked else 0, weight.data_ptr(), K, _ptr(bias),
-                                       _ptr(residual), N, norm.weight.data_ptr(), norm.bias.data_ptr(), float(norm.eps),
-                                       out.data_ptr(), N, M, K, code, int(bool(act_first)), _stream(x.device))
-        _lib.check(rc, "linear + LayerNorm")
-        return out
     splits = _split_k(M, N, K) if (add is None and row_mask is None and not col_block and not x_blocked and N % 4 == 0) else 0
     with _on(x.device):
         if splits > 1:

@@ -36,7 +36,7 @@ class Linear(nn.Linear):
 
 
 def post_is_fusable(post):
-    """post = (residual, norm[, dropout]): may the add + LayerNorm ride in a GEMM epilogue?  Only when the sub-layer's
+    """post = (residual, norm[, dropout]): may the add + LayerNorm go through dfx.ops.linear(norm=...)?  Only when the sub-layer's
     Dropout is the identity (eval mode or p = 0) - the reference applies ``norm(residual + dropout(out))``
     (/root/reference/models/deformable_transformer_single.py:635-643) also under no_grad in train mode."""
     if post is None:

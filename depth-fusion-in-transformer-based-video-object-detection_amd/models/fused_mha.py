@@ -48,8 +48,8 @@ def project_kv_stack(mhas, pool):
 def forward(mha, q_in, k_in, v_in, post=None, kv=None):
     """mha: nn.MultiheadAttention; q_in [B,Lq,E], k_in / v_in [B,Lk,E] -> [B,Lq,E]
     (= mha(q_in^T, k_in^T, v_in^T)[0]^T of the module; no caller uses the attention weights).
-    post = (residual [B,Lq,E], norm[, dropout]): -> norm(residual + dropout(output)), the add and the LayerNorm in out_proj's
-    GEMM epilogue when the dropout is the identity (eval mode).
+    post = (residual [B,Lq,E], norm[, dropout]): -> norm(residual + dropout(output)): out_proj's GEMM, then the add and the
+    LayerNorm in one add_layernorm launch (dfx.ops.linear(norm=...)) when the dropout is the identity (eval mode).
     kv [B,Lk,2E]: already projected keys / values (``project_kv`` rows); k_in / v_in are then ignored."""
     E, H = mha.embed_dim, mha.num_heads
     W, b = mha.in_proj_weight, mha.in_proj_bias

@@ -101,8 +101,8 @@ class MSDeformAttn(nn.Module):
         input_flatten [N,sum(H_l*W_l),C]; input_spatial_shapes i64 [L,2]; input_level_start_index
         i64 [L]; input_padding_mask [N,S] True = padding.  -> [N,Lq,C]   (ref :78-117)
         post = (residual, norm[, dropout]): return ``norm(residual + dropout(output))`` instead - what every caller does
-        next; on the fused GPU routes, and when the dropout is the identity (eval mode), the add and the LayerNorm ride in
-        output_proj's GEMM epilogue (dfx.ops.linear(norm=...)).
+        next; on the fused GPU routes, and when the dropout is the identity (eval mode), the add and the LayerNorm are one
+        add_layernorm launch behind output_proj's GEMM (dfx.ops.linear(norm=...)).
         value [N,S,C]: ``value_proj(input_flatten)`` with the padded tokens already zeroed, when the caller projected the
         values of several layers that share ``input_flatten`` in one launch (``project_values``); the single-level
         many-query route (block-major operands) ignores it."""

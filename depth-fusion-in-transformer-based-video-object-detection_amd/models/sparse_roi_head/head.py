@@ -121,7 +121,7 @@ class RCNNHead(nn.Module):
         q = pro_features.view(N, nr_boxes, self.d_model).permute(1, 0, 2)                 # nr,N,C
         from .. import fused_mha
         if fused_mha.usable(self.self_attn, pro_features):
-            # batch-first all the way: residual + LayerNorm ride in out_proj's GEMM epilogue
+            # batch-first all the way: residual + LayerNorm in one launch behind out_proj's GEMM
             pf = pro_features.reshape(N, nr_boxes, self.d_model)
             q = fused_mha.forward(self.self_attn, pf, pf, pf, post=(pf, self.norm1, self.dropout1)).reshape(1, N * nr_boxes, self.d_model)
         else:

@@ -53,8 +53,8 @@ def _linear_act(linear, activation, x):
 def _mha(module, q, k, v, post=None):
     """nn.MultiheadAttention on batch-first [B,L,E] tensors (no masks, attention weights unused): the fused
     GEMM + attention-kernel route in GPU inference (models/fused_mha.py), the module itself otherwise.
-    post = (residual, norm, dropout): -> norm(residual + dropout(attention output)) (in out_proj's GEMM epilogue on the fused
-    route when the dropout is the identity)."""
+    post = (residual, norm, dropout): -> norm(residual + dropout(attention output)) (one add_layernorm launch behind out_proj's GEMM
+    on the fused route when the dropout is the identity)."""
     from . import fused_mha
     if fused_mha.usable(module, q, k, v):
         return fused_mha.forward(module, q, k, v, post)
@@ -71,8 +71,8 @@ def _identity_dropout(dropout):
 
 
 def _linear_norm_add(linear, x, norm, residual=None, act=None, act_first=False, dropout=None):
-    """norm(residual + dropout(act(linear(x)))) (act_first) or norm(act(linear(x) + residual)); one MFMA GEMM launch with the
-    residual add and the LayerNorm in its epilogue in GPU inference when the Linear ends in d_model = 256 columns
+    """norm(residual + dropout(act(linear(x)))) (act_first) or norm(act(linear(x) + residual)); the MFMA GEMM with the bias and
+    the activation in its epilogue, then one add_layernorm launch, in GPU inference when the Linear ends in d_model = 256 columns
     (dfx.ops.linear(norm=...)) and the sub-layer's Dropout is the identity (eval mode), the separate ops otherwise."""
     if (_gpu_inference(x) and linear.out_features == 256 and linear.in_features % 4 == 0 and linear.weight.dtype == torch.float32
             and _identity_dropout(dropout)):
@@ -191,7 +191,7 @@ class DeformableTransformerEncoderLayer(nn.Module):
             query = (src, pos)                     # the add rides along into the projection GEMM
         else:
             query = _add_pos(src, pos)
-        if fused:       # residual add + LayerNorm in output_proj's epilogue
+        if fused:       # residual add + LayerNorm in one launch behind output_proj's GEMM
             src = self.self_attn(query, reference_points, src, spatial_shapes, level_start_index, padding_mask,
                                  post=(src, self.norm1, self.dropout1))
         else:
@@ -250,7 +250,7 @@ class _CrossFusionBlock(nn.Module):
     def forward_ffn(self, tgt):
         if (self.activation is F.gelu and tgt.is_cuda and tgt.dtype == torch.float32 and not torch.is_grad_enabled()):
             from dfx import ops as _ops            # Linear + bias + exact GELU in one MFMA GEMM
-            # Linear + bias + exact GELU + residual + LayerNorm in one MFMA GEMM
+            # ... then the residual add + LayerNorm in one launch behind it
             return _linear_norm_add(self.linear1, tgt, getattr(self, self._ffn_norm), tgt, act="gelu", act_first=True,
                                     dropout=getattr(self, self._ffn_drop))
         y = self.activation(self.linear1(tgt))

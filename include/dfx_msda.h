@@ -44,7 +44,7 @@ extern "C" {
 #define DFX_ELAUNCH (-2) /* hipGetLastError() reported a launch failure          */
 #define DFX_ERANGE (-3)  /* sizes overflow the 32-bit index space of the kernels */
 
-/* ABI version: bumped whenever a signature below changes. */
+/* ABI version: bumped whenever a signature changes or an exported symbol goes away. */
 int dfx_abi_version(void);
 
 /* Text of the last error raised on the calling thread ("" if none). */

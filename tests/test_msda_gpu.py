@@ -322,6 +322,7 @@ def _run_level_blocked(value, qproj, ref, H, W):
 @pytest.mark.parametrize("H,W,N,Lq,ref_dim,spread,raster", [
     (50, 84, 2, 4200, 2, 3.0, True),      # production map, offsets of a few pixels
     (50, 84, 8, 4200, 2, 1.0, True),      # the bench launch: 256 workgroups, one per CU
+    (50, 84, 33, 4200, 2, 2.0, True),     # 1056 items on 256 CUs: a persistent workgroup walks several items
     (50, 84, 1, 4200, 2, 30.0, True),     # large offsets, N = 1: queries split over 8 workgroups per octet
     (50, 84, 3, 300, 4, 8.0, False),      # decoder-like: few queries, box references
     (50, 84, 1, 5000, 2, 5.0, False),     # Lq != S, random references incl. outside [0,1]
@@ -339,20 +340,6 @@ def test_level_kernel_matches_oracle(msda, oracle, H, W, N, Lq, ref_dim, spread,
     assert torch.allclose(got, plain, rtol=1e-5, atol=1e-5)
     # the block-major operand layouts the model path uses: same kernel, same arithmetic -> same bits
     assert torch.equal(_run_level_blocked(value, qproj, ref, H, W), got)
-
-
-@pytest.mark.parametrize("H,W,N,Lq,ref_dim,spread", [(50, 84, 8, 4200, 2, 3.0), (50, 84, 33, 4200, 2, 2.0), (50, 84, 1, 4200, 2, 30.0),
-                                                     (13, 21, 3, 273, 4, 4.0), (55, 86, 1, 2000, 2, 4.0)])
-def test_level_kernel_prefetch_variant(msda, oracle, dfx_env, H, W, N, Lq, ref_dim, spread):
-    """DFX_LEVEL_VARIANT=1 (csrc/msda_level.hip: 512-thread workgroups, the next item's level prefetched into registers slice by
-    slice under the gather; measured slower, profiles/r04_level_variant.txt, kept for A/B runs): the same bits as the default
-    schedule - per query the arithmetic is the same - also when a workgroup walks several items (N = 33: 1056 items on 256 CUs)."""
-    value, qproj, ref = _level_case(H * 17 + W + N, H, W, N, Lq, ref_dim, spread, Lq == H * W)
-    want = _run_level_blocked(value, qproj, ref, H, W)
-    dfx_env("DFX_LEVEL_VARIANT", "1")
-    got = _run_level_blocked(value, qproj, ref, H, W)
-    dfx_env("DFX_LEVEL_VARIANT", None)
-    assert torch.equal(got, want)
 
 
 def test_level_kernel_edges(msda, oracle):

@@ -38,7 +38,7 @@ def test_binding_and_library():
     lib = ctypes.CDLL(_lib.library_path())
     for name in NAMES:
         assert hasattr(lib, name)
-    assert _lib.abi_version() == 4
+    assert _lib.abi_version() == 5
 
 
 @pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16])

@@ -36,12 +36,12 @@ def linear(*a, **k):
     b.apply_defaults()
     p = b.arguments
     x, weight = p["x"], p["weight"]
-    if p["norm"] is None or ops._FUSE_LN:          # (an unfused norm= call comes back through here for its GEMM)
+    if p["norm"] is None:          # (a norm= call comes back through here for its GEMM)
         M, K = (x.shape[1], x.shape[0] * 4) if p["x_blocked"] else (x.numel() // x.shape[-1], x.shape[-1])
         extra = "".join(t for t, on in (("+add", p["add"] is not None), ("+res", p["residual"] is not None),
                                         ("+relu", p["relu"] or p["act"] == "relu"), ("+gelu", p["act"] == "gelu"),
                                         ("+mask", p["row_mask"] is not None), (" blk-in", p["x_blocked"]),
-                                        (" blk-out", bool(p["col_block"])), ("+ln", p["norm"] is not None)) if on)
+                                        (" blk-out", bool(p["col_block"]))) if on)
         calls.append(("linear", M, weight.shape[0], K, extra))
     return _linear(*a, **k)
 
