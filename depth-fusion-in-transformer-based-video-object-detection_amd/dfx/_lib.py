@@ -23,6 +23,9 @@ SIGNATURES = {
     "dfx_msda_backward_bf16": [_p] * 6 + _DIMS + [_p, _p, _p, _p],
     "dfx_msda_backward_f16": [_p] * 6 + _DIMS + [_p, _p, _p, _p],
     "dfx_msda_fused_forward_f32": [_p, _p, _p, _p, _i, _i, _p, _l, _p, _l] + _DIMS + [_p, _p],
+    # value, shapes, lsi, ref, ref_dim, off, off_stride, logits, logit_stride, grad_out, dims, grad_value | NULL,
+    # grad_off, stride, grad_logits, stride, grad_ref | NULL, stream (csrc/msda_fused_backward.hip)
+    "dfx_msda_fused_backward_f32": [_p, _p, _p, _p, _i, _p, _l, _p, _l, _p] + _DIMS + [_p, _p, _l, _p, _l, _p, _p],
     "dfx_profile_enable": [_i],
     "dfx_tuning_reload": [],
     "dfx_profile_drain": [_p, _p, _p, _p, _i],

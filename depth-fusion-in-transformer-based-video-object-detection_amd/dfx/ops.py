@@ -225,6 +225,123 @@ def msda_fused_forward(value, spatial_shapes, level_start_index, reference_point
     return out
 
 
+def _pitched_rows(t, N, Lq, width):
+    """(tensor, row pitch in floats) of a [N,Lq,width] operand of the fused entry points: kept as it is when its rows
+    are contiguous, 16-byte aligned and one constant pitch apart (a column slice of a wider buffer), else copied."""
+    pitch = t.stride(1) if Lq > 1 else (t.stride(0) if N > 1 else width)
+    if (t.stride(2) == 1 and pitch >= width and pitch % 4 == 0 and t.data_ptr() % 16 == 0
+            and (N <= 1 or Lq <= 1 or t.stride(0) == Lq * pitch)):
+        return t, pitch
+    return t.contiguous(), width
+
+
+def _msda_fused_operands(what, value, spatial_shapes, level_start_index, reference_points, offsets, logits):
+    _check_inputs([("value", value), ("spatial_shapes", spatial_shapes), ("level_start_index", level_start_index),
+                   ("reference_points", reference_points)])
+    for name, t in (("offsets", offsets), ("logits", logits)):
+        _require(t.is_cuda and t.device == value.device, f"Not implemented on the CPU ({name} must be a CUDA tensor on {value.device})")
+    N, S, M, D = value.shape
+    L = spatial_shapes.shape[0]
+    _require(reference_points.dim() == 4 and reference_points.shape[0] == N and reference_points.shape[2] == L,
+             f"{what}: reference_points must be [N,Lq,{L},2|4] (one reference level per value level)")
+    Lq, ref_dim = reference_points.shape[1], reference_points.shape[3]
+    _require(level_start_index.shape[0] == L and L > 0 and M > 0 and offsets.dim() == 3 and offsets.shape[2] % (2 * M * L) == 0,
+             f"{what}: offsets must be [N,Lq,M*L*P*2]")
+    P = offsets.shape[2] // (2 * M * L)
+    _require(tuple(offsets.shape) == (N, Lq, M * L * P * 2) and tuple(logits.shape) == (N, Lq, M * L * P),
+             f"{what}: offsets / logits must be [N,Lq,M*L*P*2] / [N,Lq,M*L*P]")
+    _require(all(t.dtype == torch.float32 for t in (value, reference_points, offsets, logits)), f"{what} is implemented for float32")
+    _require(spatial_shapes.dtype == torch.int64 and level_start_index.dtype == torch.int64,
+             "spatial_shapes and level_start_index must be int64")
+    return N, S, M, D, L, Lq, P, ref_dim
+
+
+def _msda_fused_forward_split(value, spatial_shapes, level_start_index, reference_points, offsets, logits):
+    """dfx_msda_fused_forward_f32 on offsets and logits as two tensors (two pointers, two row strides); no autograd node."""
+    lib = _lib.load()
+    N, S, M, D, L, Lq, P, ref_dim = _msda_fused_operands("msda_fused", value, spatial_shapes, level_start_index,
+                                                         reference_points, offsets, logits)
+    offsets, off_pitch = _pitched_rows(offsets, N, Lq, M * L * P * 2)
+    logits, logit_pitch = _pitched_rows(logits, N, Lq, M * L * P)
+    out = torch.empty((N, Lq, M * D), dtype=value.dtype, device=value.device)
+    with _on(value.device):
+        rc = lib.dfx_msda_fused_forward_f32(
+            value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(), reference_points.data_ptr(),
+            ref_dim, L, offsets.data_ptr(), off_pitch, logits.data_ptr(), logit_pitch,
+            N, S, M, D, L, Lq, P, out.data_ptr(), _stream(value.device))
+    _lib.check(rc, "msda_fused")
+    return out
+
+
+def msda_fused_backward(grad_out, value, spatial_shapes, level_start_index, reference_points, offsets, logits,
+                        need_value=True, need_ref=False):
+    """Gradients of msda_fused from its inputs alone (include/dfx_msda.h, dfx_msda_fused_backward_f32: the kernel
+    recomputes the softmax weights and the locations).  grad_out [N,Lq,M*D]; reference_points contiguous; offsets /
+    logits as for msda_fused (rows may be column slices of a wider buffer).
+    -> (grad_value [N,S,M,D] | None, grad_offsets like offsets, grad_logits like logits, grad_ref like reference_points | None)
+    grad_value is summed with float atomics and is only computed (and its buffer only allocated) with need_value; the
+    other three are plain stores: two calls on the same inputs give the same bits."""
+    lib = _lib.load()
+    N, S, M, D, L, Lq, P, ref_dim = _msda_fused_operands("msda_fused_backward", value, spatial_shapes, level_start_index,
+                                                         reference_points, offsets, logits)
+    grad_out = grad_out.contiguous()
+    _require(grad_out.is_cuda and grad_out.dtype == torch.float32 and grad_out.numel() == N * Lq * M * D,
+             "msda_fused_backward: grad_out must be [N,Lq,M*D] fp32 on the GPU")
+    offsets, off_pitch = _pitched_rows(offsets, N, Lq, M * L * P * 2)
+    logits, logit_pitch = _pitched_rows(logits, N, Lq, M * L * P)
+    dev = value.device
+    grad_value = torch.zeros_like(value) if need_value else None            # the one buffer the kernel accumulates into
+    grad_off = torch.empty((N, Lq, M * L * P * 2), dtype=torch.float32, device=dev)
+    grad_logits = torch.empty((N, Lq, M * L * P), dtype=torch.float32, device=dev)
+    grad_ref = torch.empty((N, Lq, L, ref_dim), dtype=torch.float32, device=dev) if need_ref else None
+    with _on(dev):
+        rc = lib.dfx_msda_fused_backward_f32(
+            value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(), reference_points.data_ptr(), ref_dim,
+            offsets.data_ptr(), off_pitch, logits.data_ptr(), logit_pitch, grad_out.data_ptr(),
+            N, S, M, D, L, Lq, P, _ptr(grad_value), grad_off.data_ptr(), M * L * P * 2, grad_logits.data_ptr(), M * L * P,
+            _ptr(grad_ref), _stream(dev))
+    _lib.check(rc, "msda_fused_backward")
+    return grad_value, grad_off, grad_logits, grad_ref
+
+
+class _MSDAFusedFunction(torch.autograd.Function):
+    """apply(value, spatial_shapes, level_start_index, reference_points, offsets, logits): saves its inputs only; the
+    backward kernel recomputes the rest."""
+
+    @staticmethod
+    def forward(ctx, value, spatial_shapes, level_start_index, reference_points, offsets, logits):
+        ctx.save_for_backward(value, spatial_shapes, level_start_index, reference_points, offsets, logits)
+        return _msda_fused_forward_split(value, spatial_shapes, level_start_index, reference_points, offsets, logits)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        need = ctx.needs_input_grad
+        gv, go, gl, gr = msda_fused_backward(grad_output, *ctx.saved_tensors, need_value=need[0], need_ref=need[3])
+        return gv, None, None, gr, go if need[4] else None, gl if need[5] else None
+
+
+def msda_fused(value, spatial_shapes, level_start_index, reference_points, offsets, logits, n_levels, n_points):
+    """softmax + location arithmetic + sampling in one launch, trainable (include/dfx_msda.h,
+    dfx_msda_fused_forward_f32 / dfx_msda_fused_backward_f32).
+
+    value            [N,S,M,D] fp32, contiguous (M = 8, D = 32)
+    reference_points [N,Lq,n_levels,2|4]
+    offsets          [N,Lq,M*L*P*2]  raw sampling_offsets Linear output   \\ last dimension contiguous; rows may be
+    logits           [N,Lq,M*L*P]    raw attention_weights Linear output  / column slices of one wider buffer
+    -> [N,Lq,M*D], the bits of msda_fused_forward on the concatenated rows.
+    With grad mode on and value, reference_points, offsets or logits requiring a gradient the result carries it back
+    through msda_fused_backward (gradients for exactly the inputs that ask for one); otherwise no autograd node is made."""
+    _require(spatial_shapes.shape[0] == n_levels and logits.shape[-1] == value.shape[2] * n_levels * n_points,
+             "msda_fused: spatial_shapes rows must equal n_levels and logits be [N,Lq,M*n_levels*n_points]")
+    reference_points = reference_points.contiguous()
+    # (the operands are validated once, by the forward helper both branches end in)
+    if torch.is_grad_enabled() and (value.requires_grad or reference_points.requires_grad or offsets.requires_grad
+                                    or logits.requires_grad):
+        return _MSDAFusedFunction.apply(value, spatial_shapes, level_start_index, reference_points, offsets, logits)
+    return _msda_fused_forward_split(value, spatial_shapes, level_start_index, reference_points, offsets, logits)
+
+
 def level_supported(value_like, H, W, Lq, n_heads, head_dim, n_levels, n_points, n_ref_levels):
     """Single-level attention the level-in-LDS kernel (csrc/msda_level.hip) should run: its
     geometry, a level that fits the CU's LDS, and enough queries to pay for staging the level."""

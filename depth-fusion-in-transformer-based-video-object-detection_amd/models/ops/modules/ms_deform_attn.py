@@ -3,13 +3,17 @@
 
 Same constructor, parameter names (``sampling_offsets``, ``attention_weights``,
 ``value_proj``, ``output_proj`` -> same state_dict keys), initialisation and forward
-signature as the reference.  Two execution routes:
+signature as the reference.  Three execution routes:
 
 * inference on the GPU with the production head geometry (8 heads x 32 channels, 4 points,
   <= 4 levels, fp32): ONE GEMM produces [offsets | logits] per query and the fused kernel
   (csrc/msda_fused.hip) does softmax, location arithmetic and sampling in one launch;
-* anything else (training, fp64, odd geometry): the reference's op sequence with the
-  autograd operator ``MSDeformAttnFunction`` (csrc/msda_forward.hip / msda_backward.hip).
+* training (grad mode) on the GPU with the same geometry, fp32, no autocast and one reference level
+  per value level: the four Linear layers under autograd, and between them the same fused kernel
+  with the fused backward (csrc/msda_fused_backward.hip) behind it (``dfx.ops.msda_fused``);
+* anything else (fp64, autocast, odd geometry, the temporal decoder's flat read in grad mode): the
+  reference's op sequence with the autograd operator ``MSDeformAttnFunction``
+  (csrc/msda_forward.hip / msda_backward.hip).
 
 There is no CPU route: like the reference's op (ms_deform_attn.h:38) it raises on CPU tensors.
 """
@@ -25,6 +29,11 @@ from models.fused import Linear, apply_post, post_is_fusable
 
 from dfx import ops as _ops
 from ..functions import ms_deform_attn_func as _func
+
+
+# MSDeformAttn in grad mode on the fused forward + fused backward (csrc/msda_fused_backward.hip); DFX_MSDA_TRAIN=0 keeps
+# the reference's op sequence with MSDeformAttnFunction (A/B runs).  Read once at import.
+MSDA_TRAIN = os.environ.get("DFX_MSDA_TRAIN", "1") != "0"
 
 
 def _is_power_of_2(n):
@@ -162,6 +171,16 @@ class MSDeformAttn(nn.Module):
             if input_padding_mask is not None:
                 value = value.masked_fill(input_padding_mask[..., None], float(0))
         value = value.view(N, S, M, D)
+
+        if (MSDA_TRAIN and value.is_cuda and not torch.is_autocast_enabled() and reference_points.shape[2] == L
+                and value.dtype == query.dtype == reference_points.dtype == torch.float32
+                and _ops.fused_supported(value, M, D, L, P, reference_points.shape[2])):
+            # grad mode on the fused front end: the four Linear layers stay the modules they are, what lies between
+            # them is one launch forwards and one backwards (csrc/msda_fused.hip, csrc/msda_fused_backward.hip);
+            # no sampling_locations / attention_weights tensors exist, the node saves the Linear outputs only
+            sampled = _ops.msda_fused(value.contiguous(), input_spatial_shapes, input_level_start_index, reference_points,
+                                      self.sampling_offsets(query), self.attention_weights(query), L, P)
+            return apply_post(post, self.output_proj(sampled))
 
         offsets = self.sampling_offsets(query).view(N, Lq, M, L, P, 2)
         weights = F.softmax(self.attention_weights(query).view(N, Lq, M, L * P), -1).view(N, Lq, M, L, P)

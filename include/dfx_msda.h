@@ -152,6 +152,34 @@ int dfx_msda_fused_forward_f32(const float *value, const int64_t *shapes, const 
                                float *out, void *stream);
 
 /*
+ * Backward of dfx_msda_fused_forward_f32 (training; csrc/msda_fused_backward.hip) from the forward's own raw
+ * inputs: the kernel recomputes the softmax weights and the locations, the caller saves nothing else.
+ * Replaces ms_deform_attn_cuda_backward (ms_deform_attn_cuda.cu:83-153) together with what autograd runs
+ * behind it for the reference's models/ops/modules/ms_deform_attn.py:98-110 (softmax, divide, broadcast add).
+ * Geometry of the fused forward (fp32, M = 8, D = 32, P = 4, 1 <= L <= 4, ref_dim 2 or 4) with Lr == L only;
+ * the same argument checks (strides multiples of 4 and not smaller than the row, 16-byte alignment, sizes).
+ *   grad_out    [N,Lq,M*D]
+ *   grad_value  [N,S,M,D] ACCUMULATED into with float atomics: the caller zero-fills it.  May be NULL (the
+ *               memory needs no gradient): the kernel then contains no atomics at all.
+ *   grad_off    like off, row stride grad_off_stride      \  WRITTEN in full with plain stores (every element
+ *   grad_logits like logits, row stride grad_logit_stride  > has one owning wave): the caller need not
+ *   grad_ref    [N,Lq,L,ref_dim], may be NULL             /  initialise them; two calls give the same bits.
+ * N*Lq == 0 returns DFX_OK without a launch; S == 0 writes zeros to the three small
+ * gradients.  An addition to the ABI: dfx_abi_version() stays.
+ */
+int dfx_msda_fused_backward_f32(const float *value, const int64_t *shapes, const int64_t *lsi,
+                                const float *ref, int ref_dim,
+                                const float *off, long off_stride,
+                                const float *logits, long logit_stride,
+                                const float *grad_out,
+                                int N, int S, int M, int D, int L, int Lq, int P,
+                                float *grad_value,
+                                float *grad_off, long grad_off_stride,
+                                float *grad_logits, long grad_logit_stride,
+                                float *grad_ref,
+                                void *stream);
+
+/*
  * The same fused operator for single-level attention with the whole level resident in LDS
  * (csrc/msda_level.hip): L = 1, one reference level, P = 4, M = 8, D = 32, any Lq.  A workgroup
  * stages 8 channels of one head of every token of the H x W map (zero-bordered) into LDS and the
