@@ -645,6 +645,46 @@ def conv1x1_pair(x1, x2, weight, bias=None, relu=False):
     return out
 
 
+def conv1x1_chain_supported(Co, K1, K2, C1, HW):
+    """Shapes dfx_conv1x1_chain_f32 covers (include/dfx_gemm.h): a wave keeps its [K, 32] activation panel and its
+    [C1, 32] accumulators in registers."""
+    K = K1 + K2
+    return (Co > 0 and Co % 32 == 0 and C1 > 0 and C1 % 32 == 0 and K % 32 == 0 and K1 % 16 == 0 and K2 % 16 == 0 and
+            K <= 128 and C1 <= 256 and HW % 4 == 0 and max(Co, 256) * HW * 4 < (1 << 31))
+
+
+def conv1x1_chain(x, w3, b3, w1, b1, residual=None, x2=None, relu_z=True):
+    """A bottleneck's last 1x1 convolution and the next block's first one as one launch (include/dfx_gemm.h,
+    dfx_conv1x1_chain_f32):  y = relu(w3 x [x ; x2] + b3 + residual),  z = relu_z?(w1 x y + b1)  ->  (y, z).
+    x [N,K1,H,W], x2 [N,K2,H,W] or None, w3 [Co,K1+K2], w1 [C1,Co], residual [N,Co,H,W] or None.
+    A shape the fused kernel does not cover runs as the two separate launches (conv1x1 / conv1x1_pair, then conv1x1):
+    the results are the same bit for bit."""
+    lib = _lib.load()
+    Nb, K1, H, W = x.shape
+    K2 = 0 if x2 is None else x2.shape[1]
+    Co, C1, HW = w3.shape[0], w1.shape[0], H * W
+    w3, w1 = w3.reshape(Co, -1), w1.reshape(C1, -1)
+    named = [("x", x), ("w3", w3), ("w1", w1)] + [(n, t) for n, t in (("x2", x2), ("b3", b3), ("b1", b1), ("residual", residual))
+                                                  if t is not None]
+    _check_inputs(named)
+    _require(x.dtype == torch.float32 and w3.shape[1] == K1 + K2 and w1.shape[1] == Co and
+             (x2 is None or x2.shape == (Nb, K2, H, W)), "conv1x1_chain: fp32, w3 [Co,K1+K2], w1 [C1,Co], x2 [N,K2,H,W]")
+    _require(x2 is None or residual is None, "conv1x1_chain: the two-segment form takes no residual")
+    if residual is not None:
+        _require(residual.shape == (Nb, Co, H, W), "residual must match the output")
+    if not conv1x1_chain_supported(Co, K1, K2, C1, HW) or Nb == 0:
+        y = (conv1x1(x, w3, b3, residual=residual, relu=True) if x2 is None else conv1x1_pair(x, x2, w3, b3, relu=True))
+        return y, conv1x1(y, w1, b1, relu=relu_z)
+    y = torch.empty((Nb, Co, H, W), dtype=x.dtype, device=x.device)
+    z = torch.empty((Nb, C1, H, W), dtype=x.dtype, device=x.device)
+    with _on(x.device):
+        rc = lib.dfx_conv1x1_chain_f32(w3.data_ptr(), x.data_ptr(), K1 * HW, K1, _ptr(x2), K2 * HW, K2, _ptr(b3),
+                                       _ptr(residual), Co * HW, y.data_ptr(), Co * HW, w1.data_ptr(), _ptr(b1),
+                                       z.data_ptr(), C1 * HW, Co, C1, HW, Nb, int(bool(relu_z)), _stream(x.device))
+    _lib.check(rc, "conv1x1_chain")
+    return y, z
+
+
 def _dynamic_conv_checks(feats, params, norm1, norm2):
     _check_inputs([("feats", feats), ("norm1.weight", norm1.weight), ("norm2.weight", norm2.weight)])
     K, R, C = feats.shape

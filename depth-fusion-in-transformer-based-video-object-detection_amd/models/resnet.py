@@ -16,6 +16,10 @@ import os
 from dfx import ops as _ops
 
 _PAIR_SHORTCUT = os.environ.get("DFX_PAIR_SHORTCUT", "1") == "1"      # A/B switch of the fused conv3 + shortcut product
+_CONV_CHAIN = os.environ.get("DFX_CONV_CHAIN", "1") == "1"            # A/B switch of conv3 + the next block's conv1 in one launch
+# widest conv1 the chain takes: 256 output channels (layer2[3] -> layer3[0]) leave the fused kernel one workgroup per CU and
+# measured 4 % slower than the two launches at 32 frames, every narrower producer 7-25 % faster (profiles/r10_conv1x1_chain.txt)
+_CONV_CHAIN_MAX_C1 = int(os.environ.get("DFX_CONV_CHAIN_MAX_C1", "128"))
 
 
 def _fold(conv, bn):
@@ -72,19 +76,39 @@ class Bottleneck(nn.Module):
             self._folded = (key, f)
         return self._folded[1]
 
-    def forward_fused(self, x):
+    def chain_conv1(self):
+        """Folded (weight, bias) of conv1 for the block in front to compute with its own conv3 (dfx.ops.conv1x1_chain), or
+        None: torchvision puts a stage's stride on conv2, so conv1 is a stride-1 1x1 product over the map it is handed."""
+        c = self.conv1
+        if c.kernel_size != (1, 1) or c.stride != (1, 1) or c.padding != (0, 0) or c.groups != 1:
+            return None
+        return self._folded_params()[0]
+
+    def forward_fused(self, x, z=None, nxt=None):
         """Inference on the GPU: frozen BN folded into the convolutions.  The 3x3 convolutions run on the
         hand-written Winograd / implicit-GEMM kernels (dfx.ops.ConvPlan, csrc/conv_wino.hip,
         csrc/conv_igemm.hip), the 1x1 convolutions on the hand-written MFMA GEMM (dfx.ops.conv1x1), each
-        with bias / residual / ReLU in its epilogue.  No CPU route."""
+        with bias / residual / ReLU in its epilogue.  No CPU route.
+
+        z: this block's conv1 output where the block in front has already computed it.  nxt: the folded conv1 of the block
+        that follows (chain_conv1()); the result is then (y, z_next) with z_next that block's conv1 output from the same
+        launch as conv3 (csrc/conv1x1_chain.hip), or None where the fused kernel does not cover the shape."""
         (w1, b1), plan2, (w3, b3), down, pair = self._folded_params()
-        out = self._conv1x1(0, x, w1, b1, relu=True)
+        out = z if z is not None else self._conv1x1(0, x, w1, b1, relu=True)
         out = plan2(out)
-        if pair is not None and (out.shape[2] * out.shape[3]) % 4 == 0 and out.shape[2:] == x.shape[2:]:
-            return _ops.conv1x1_pair(out, x.contiguous(), pair[0], pair[1], relu=True)
+        hw = out.shape[2] * out.shape[3]
+        chain = nxt is not None and hw % 4 == 0 and nxt[0].shape[0] <= _CONV_CHAIN_MAX_C1
+        if pair is not None and hw % 4 == 0 and out.shape[2:] == x.shape[2:]:
+            if chain and _ops.conv1x1_chain_supported(pair[0].shape[0], out.shape[1], x.shape[1], nxt[0].shape[0], hw):
+                return _ops.conv1x1_chain(out, pair[0], pair[1], nxt[0], nxt[1], x2=x.contiguous())
+            y = _ops.conv1x1_pair(out, x.contiguous(), pair[0], pair[1], relu=True)
+            return y if nxt is None else (y, None)
         if down is not None:
             x = self._conv1x1(1, x, down[0], down[1], relu=False, stride=self.downsample[0].stride[0])
-        return self._conv1x1(2, out, w3, b3, relu=True, residual=x)
+        if chain and _ops.conv1x1_chain_supported(w3.shape[0], out.shape[1], 0, nxt[0].shape[0], hw):
+            return _ops.conv1x1_chain(out, w3, b3, nxt[0], nxt[1], residual=x)
+        y = self._conv1x1(2, out, w3, b3, relu=True, residual=x)
+        return y if nxt is None else (y, None)
 
     def _conv1x1(self, slot, x, w, b, relu, residual=None, stride=1):
         """1x1 convolution + bias (+ residual) (+ ReLU): the MFMA GEMM over [Ci] x [H*W] when its 16-byte
@@ -163,8 +187,26 @@ class ResNet50(nn.Module):
     def run_stage(self, stage, x, fused=False):
         if not fused:
             return stage(x)
-        for block in stage:
-            x = block.forward_fused(x)
+        # conv3 of a layer1 / layer2 block also produces the conv1 of the block behind it - the next block of the stage or
+        # the first one of the next stage - in the same launch where that measured faster (_CONV_CHAIN_MAX_C1): these producers are
+        # HBM-bound on writing their 256- / 512-channel map, which the standalone conv1 would read back in full.  layer3 /
+        # layer4 producers are MFMA-bound and stay as they are.  Between two stages the pair (map, its conv1) waits in
+        # _chain_carry; it is used only for the very tensor it was computed from.
+        carry, self._chain_carry = self.__dict__.get("_chain_carry"), None
+        z = carry[1] if carry is not None and carry[0] is x else None
+        follower = {id(self.layer1): self.layer2, id(self.layer2): self.layer3}.get(id(stage)) if _CONV_CHAIN else None
+        blocks = list(stage)
+        for i, block in enumerate(blocks):
+            succ = None
+            if follower is not None:
+                succ = blocks[i + 1] if i + 1 < len(blocks) else follower[0]
+            nxt = succ.chain_conv1() if succ is not None else None
+            if nxt is None:
+                x, z = block.forward_fused(x, z), None
+            else:
+                x, z = block.forward_fused(x, z, nxt)
+        if z is not None:
+            self._chain_carry = (x, z)
         return x
 
     def forward(self, x):

@@ -49,6 +49,19 @@
  * with W = [W3 | Wd] (frozen-BN scales folded in, bias = shift3 + shiftd): the shortcut map is neither written nor
  * read back as a residual.  X1 [batch,K1,HW], X2 [batch,K2,HW] (image strides in floats), W [Co,K1+K2] row-major,
  * Y [batch,Co,HW]; K1, K2 multiples of 16, HW of 4.
+ *
+ * dfx_conv1x1_chain_f32: a bottleneck's last 1x1 convolution AND the first 1x1 convolution of the block that follows it
+ * (torchvision Bottleneck, /root/reference/models/backbone_scratch.py:102-141: the stride sits on conv2, so every conv1 is a
+ * stride-1 product over the map its predecessor wrote) in one launch:
+ *   Y[n] = relu(W3 x [X1[n] ; X2[n]] + b3 + R[n])     [Co, HW]
+ *   Z[n] = act_z(W1 x Y[n] + b1)                      [C1, HW]   act_z 0: none, 1: ReLU
+ * Z is computed from the Y tile while it is still in registers: the Co-channel map is written once and not read back.
+ * X2 (with K2 > 0: the two-segment form of dfx_conv1x1_pair_f32), R, b3 and b1 are optional (NULL; K2 = 0 without X2).
+ * W3 [Co, K1+K2], W1 [C1, Co] row-major; X1 [batch,K1,HW], X2 [batch,K2,HW], R and Y [batch,Co,HW], Z [batch,C1,HW] with
+ * image strides in floats.  Covered: Co, C1 and K1+K2 multiples of 32 (K1, K2 of 16), K1+K2 <= 128, C1 <= 256 (the
+ * activation panel and the Z accumulators of a wave live in registers), HW a multiple of 4; any other shape returns
+ * DFX_EINVAL without a launch and the caller runs the two products as separate calls.  Y and Z are bit-equal to
+ * dfx_gemm_f32 / dfx_conv1x1_pair_f32 followed by dfx_gemm_f32 on the same operands (same k order, same epilogue order).
  */
 #ifndef DFX_GEMM_H
 #define DFX_GEMM_H
@@ -74,6 +87,12 @@ int dfx_gemm_splitk_f32(const float *A, long lda, const float *B, long ldb, int 
 int dfx_conv1x1_pair_f32(const float *W, const float *X1, long strideX1, int K1,
                          const float *X2, long strideX2, int K2, const float *bias,
                          float *Y, long strideY, int Co, int HW, int batch, int act, void *stream);
+
+int dfx_conv1x1_chain_f32(const float *W3, const float *X1, long strideX1, int K1,
+                          const float *X2, long strideX2, int K2, const float *b3,
+                          const float *R, long strideR, float *Y, long strideY,
+                          const float *W1, const float *b1, float *Z, long strideZ,
+                          int Co, int C1, int HW, int batch, int act_z, void *stream);
 
 #ifdef __cplusplus
 }

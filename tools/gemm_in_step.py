@@ -2,7 +2,7 @@
 
     python tools/gemm_in_step.py [frames]
 
-`dfx.ops.linear / conv1x1 / conv1x1_pair` are wrapped to note the shape of every call; the library's own launch stamps
+`dfx.ops.linear / conv1x1 / conv1x1_pair / conv1x1_chain` are wrapped to note the shape of every call; the library's own launch stamps
 (dfx_profile_*, the ones bench.py's `roofline` uses) come back in launch order and are matched one to one.  One clip at a
 time on one stream (`bench.py --pipeline 0`'s schedule).
 """
@@ -28,7 +28,7 @@ x = torch.randn(F_, 4, 800, 1333, device=dev)
 calls = []
 EACH = os.environ.get("EACH")          # "M,N,K": every launch of that conv1x1 shape on its own line, with the operands' addresses
 where = []
-_linear, _conv1x1, _pair = ops.linear, ops.conv1x1, ops.conv1x1_pair
+_linear, _conv1x1, _pair, _chain = ops.linear, ops.conv1x1, ops.conv1x1_pair, ops.conv1x1_chain
 
 
 def linear(*a, **k):
@@ -63,11 +63,21 @@ def conv1x1_pair(x1, x2, weight, bias=None, relu=False):
     return _pair(x1, x2, weight, bias, relu)
 
 
+def conv1x1_chain(x, w3, b3, w1, b1, residual=None, x2=None, relu_z=True):
+    n, c1, h, w = x.shape
+    k2 = 0 if x2 is None else x2.shape[1]
+    if ops.conv1x1_chain_supported(w3.shape[0], c1, k2, w1.shape[0], h * w):
+        # one stamp with the flops of both products: 2 Co HW (K + C1); an unsupported shape comes back through the wrappers above
+        calls.append(("conv1x1 chain", w3.shape[0], n * h * w, c1 + k2 + w1.shape[0],
+                      ("+res" if residual is not None else "") + f"+conv1 {w1.shape[0]}"))
+    return _chain(x, w3, b3, w1, b1, residual, x2, relu_z)
+
+
 with torch.no_grad():
     for _ in range(2):
         runner(x)
     torch.cuda.synchronize()
-    ops.linear, ops.conv1x1, ops.conv1x1_pair = linear, conv1x1, conv1x1_pair
+    ops.linear, ops.conv1x1, ops.conv1x1_pair, ops.conv1x1_chain = linear, conv1x1, conv1x1_pair, conv1x1_chain
     ops.profile_start()
     runner(x)
     torch.cuda.synchronize()
