@@ -5,6 +5,7 @@ Mirrors the host half of the reference's CUDA op
 argument checks, the same dimension derivation (L from spatial_shapes.size(0), Lq from
 sampling_loc.size(1), P from sampling_loc.size(4)), fresh output tensors.
 """
+import ctypes
 import os
 
 import torch
@@ -23,9 +24,6 @@ USE_LEVEL_KERNEL = os.environ.get("DFX_MSDA_LEVEL", "1") == "1"
 LEVEL_MIN_QUERIES = 1024
 # convolutions of <= 4 input channels from an LDS-resident input tile (csrc/conv_tile.hip); 0: on the implicit GEMM (A/B runs)
 USE_TILE_CONV = os.environ.get("DFX_TILE_CONV", "1") == "1"
-# msda_fused_forward takes operands in the reference layouts, where the level kernel is slower than the
-# wave-per-query kernel (33 vs 26 us at the encoder geometry): it uses it only when this is set (parity tests).
-LEVEL_ON_REFERENCE_LAYOUTS = False
 
 # Measurement hook (bench.py): profile_start() makes every fused MSDA kernel stamp its own begin / end
 # timestamps (include/dfx_msda.h, dfx_profile_*); profile_stop() returns [(seconds, algorithmic_bytes,
@@ -41,7 +39,6 @@ def reload_tuning():
 
 
 def profile_stop(cap=65536):
-    import ctypes
     lib = _lib.load()
     lib.dfx_profile_enable(0)
     ms = (ctypes.c_float * cap)()
@@ -111,6 +108,24 @@ def _on(dev):
     return torch.cuda.device(dev)
 
 
+_ENTRIES = {}      # name -> bound ctypes function of the loaded library
+
+
+def _call(what, name, dev, *args):
+    """One launch: the library's `name`(*args, current stream of `dev`) with `dev` current; a failure raises as `what`."""
+    fn = _ENTRIES.get(name)
+    if fn is None:
+        fn = _ENTRIES[name] = getattr(_lib.load(), name)
+    current = torch.cuda.current_device()
+    if _raw_stream is not None and dev.index in (None, current):     # one process per GPU: always (host time, see _stream)
+        rc = fn(*args, _raw_stream(current))
+    else:
+        with _on(dev):
+            rc = fn(*args, _stream(dev))
+    if rc != 0:
+        _lib.check(rc, what)
+
+
 def _operand_dtypes(what, value, sampling_loc, attn_weight):
     """The operator's dtype contract -> library suffix: fp32 / fp64 with locations and weights of the same dtype, or a
     bf16 / fp16 value with fp32 locations and weights (what MSDeformAttn produces under torch.autocast)."""
@@ -126,7 +141,6 @@ def _operand_dtypes(what, value, sampling_loc, attn_weight):
 
 
 def msda_forward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, im2col_step=64):
-    lib = _lib.load()
     _check_inputs([("value", value), ("spatial_shapes", spatial_shapes),
                    ("level_start_index", level_start_index), ("sampling_loc", sampling_loc),
                    ("attn_weight", attn_weight)])
@@ -137,18 +151,14 @@ def msda_forward(value, spatial_shapes, level_start_index, sampling_loc, attn_we
     _require(sampling_loc.numel() >= N * Lq * M * L * P * 2 and attn_weight.numel() >= N * Lq * M * L * P,
              "sampling_loc / attn_weight smaller than N*Lq*M*L*P")
     out = torch.empty((N, Lq, M * D), dtype=value.dtype, device=value.device)
-    fn = getattr(lib, "dfx_msda_forward_" + suffix)
-    with _on(value.device):
-        rc = fn(value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(),
-                sampling_loc.data_ptr(), attn_weight.data_ptr(), N, S, M, D, L, Lq, P,
-                out.data_ptr(), _stream(value.device))
-    _lib.check(rc, "ms_deform_attn_forward")
+    _call("ms_deform_attn_forward", "dfx_msda_forward_" + suffix, value.device,
+          value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(), sampling_loc.data_ptr(),
+          attn_weight.data_ptr(), N, S, M, D, L, Lq, P, out.data_ptr())
     return out
 
 
 def msda_backward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output,
                   im2col_step=64):
-    lib = _lib.load()
     _check_inputs([("value", value), ("spatial_shapes", spatial_shapes),
                    ("level_start_index", level_start_index), ("sampling_loc", sampling_loc),
                    ("attn_weight", attn_weight), ("grad_output", grad_output)])
@@ -161,13 +171,10 @@ def msda_backward(value, spatial_shapes, level_start_index, sampling_loc, attn_w
     grad_value = torch.zeros(value.shape, dtype=torch.float32, device=value.device) if half else torch.zeros_like(value)
     grad_loc = torch.zeros_like(sampling_loc)
     grad_aw = torch.zeros_like(attn_weight)
-    fn = getattr(lib, "dfx_msda_backward_" + suffix)
-    with _on(value.device):
-        rc = fn(value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(),
-                sampling_loc.data_ptr(), attn_weight.data_ptr(), grad_output.data_ptr(),
-                N, S, M, D, L, Lq, P, grad_value.data_ptr(), grad_loc.data_ptr(), grad_aw.data_ptr(),
-                _stream(value.device))
-    _lib.check(rc, "ms_deform_attn_backward")
+    _call("ms_deform_attn_backward", "dfx_msda_backward_" + suffix, value.device,
+          value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(), sampling_loc.data_ptr(),
+          attn_weight.data_ptr(), grad_output.data_ptr(), N, S, M, D, L, Lq, P, grad_value.data_ptr(), grad_loc.data_ptr(),
+          grad_aw.data_ptr())
     if half:
         grad_value = grad_value.to(value.dtype)
     return [grad_value, grad_loc, grad_aw]
@@ -177,52 +184,6 @@ def fused_supported(value, M, D, L, P, Lr):
     """Geometry the fused front-end kernel covers (else callers take the unfused op)."""
     return (value.is_cuda and value.dtype == torch.float32 and M == 8 and D == 32 and P == 4
             and 1 <= L <= 4 and (Lr == L or L == 1))
-
-
-def msda_fused_forward(value, spatial_shapes, level_start_index, reference_points, qproj, n_levels, n_points):
-    """softmax + location arithmetic + sampling in one launch (include/dfx_msda.h,
-    dfx_msda_fused_forward_f32).
-
-    value            [N,S,M,D] fp32, contiguous
-    reference_points [N,Lq,Lr,2|4]
-    qproj            [N,Lq,3*M*L*P] = one row per query holding the raw sampling_offsets
-                     Linear output (M*L*P*2 floats) followed by the raw attention_weights
-                     Linear output (M*L*P floats)
-    -> [N,Lq,M*D]
-    """
-    lib = _lib.load()
-    reference_points = reference_points.contiguous()
-    _check_inputs([("value", value), ("spatial_shapes", spatial_shapes),
-                   ("level_start_index", level_start_index), ("reference_points", reference_points),
-                   ("qproj", qproj)])
-    N, S, M, D = value.shape
-    L, P = n_levels, n_points
-    _require(spatial_shapes.shape[0] == L, "spatial_shapes rows must equal n_levels")
-    Lq, Lr, ref_dim = reference_points.shape[1], reference_points.shape[2], reference_points.shape[3]
-    mlp = M * L * P
-    _require(qproj.shape == (N, Lq, 3 * mlp) and qproj.dtype == torch.float32, "qproj has the wrong shape/dtype")
-    _require(reference_points.dtype == torch.float32 and reference_points.shape[0] == N, "bad reference_points")
-    out = torch.empty((N, Lq, M * D), dtype=value.dtype, device=value.device)
-    base = qproj.data_ptr()
-    host = getattr(spatial_shapes, "_dfx_host", None)
-    level = (USE_LEVEL_KERNEL and LEVEL_ON_REFERENCE_LAYOUTS and host is not None and L == 1 and Lr == 1 and M == 8 and D == 32
-             and P == 4 and S == host[0][0] * host[0][1] and Lq >= LEVEL_MIN_QUERIES
-             and lib.dfx_msda_fused_level_fits(host[0][0], host[0][1]))
-    with _on(value.device):
-        if level:  # the whole level lives in LDS
-            import ctypes
-            ly = _lib.LevelLayout(S * 256, 256, 32, 8, 4, 3 * mlp, 8, 3 * mlp, 4, 256, 32, 8, 4)   # reference layouts
-            rc = lib.dfx_msda_fused_level_forward_f32(
-                value.data_ptr(), reference_points.data_ptr(), ref_dim, base, base + 2 * mlp * 4, ctypes.byref(ly),
-                N, host[0][0], host[0][1], Lq, out.data_ptr(), _stream(value.device))
-        else:
-            rc = lib.dfx_msda_fused_forward_f32(
-                value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(),
-                reference_points.data_ptr(), ref_dim, Lr,
-                base, 3 * mlp, base + 2 * mlp * 4, 3 * mlp,
-                N, S, M, D, L, Lq, P, out.data_ptr(), _stream(value.device))
-    _lib.check(rc, "msda_fused_forward")
-    return out
 
 
 def _pitched_rows(t, N, Lq, width):
@@ -235,42 +196,85 @@ def _pitched_rows(t, N, Lq, width):
     return t.contiguous(), width
 
 
-def _msda_fused_operands(what, value, spatial_shapes, level_start_index, reference_points, offsets, logits):
-    _check_inputs([("value", value), ("spatial_shapes", spatial_shapes), ("level_start_index", level_start_index),
-                   ("reference_points", reference_points)])
-    for name, t in (("offsets", offsets), ("logits", logits)):
-        _require(t.is_cuda and t.device == value.device, f"Not implemented on the CPU ({name} must be a CUDA tensor on {value.device})")
+def _msda_fused_operands(what, value, spatial_shapes, level_start_index, reference_points, rows, flat_read=False):
+    """The operand contract of the fused taps kernel (include/dfx_msda.h), stated once for the forward, the trainable form
+    and the backward: shapes and dtypes first, then placement (contiguous, on one GPU).
+    rows: ((name, tensor, k), ...), the per-query operands, each [N,Lq,k*M*L*P] fp32 on value's device (rows may be
+    strided).  flat_read admits Lr != L reference levels over a single value level (the temporal decoder's flat read,
+    csrc/msda_fused.hip); without it there is one reference level per value level.
+    -> N, S, M, D, L, Lq, P, Lr, ref_dim"""
+    # (messages are only formatted on failure: this runs for every launch of the path)
+    if value.dim() != 4 or spatial_shapes.dim() != 2:
+        raise RuntimeError(f"{what}: value must be [N,S,M,D], spatial_shapes [L,2]")
     N, S, M, D = value.shape
     L = spatial_shapes.shape[0]
-    _require(reference_points.dim() == 4 and reference_points.shape[0] == N and reference_points.shape[2] == L,
-             f"{what}: reference_points must be [N,Lq,{L},2|4] (one reference level per value level)")
+    Lr = reference_points.shape[2] if reference_points.dim() == 4 else -1
+    if Lr < 0 or reference_points.shape[0] != N or not (Lr == L or (flat_read and L == 1)):
+        raise RuntimeError(f"{what}: reference_points must be [N,Lq,{L},2|4] (one reference level per value level)")
     Lq, ref_dim = reference_points.shape[1], reference_points.shape[3]
-    _require(level_start_index.shape[0] == L and L > 0 and M > 0 and offsets.dim() == 3 and offsets.shape[2] % (2 * M * L) == 0,
-             f"{what}: offsets must be [N,Lq,M*L*P*2]")
-    P = offsets.shape[2] // (2 * M * L)
-    _require(tuple(offsets.shape) == (N, Lq, M * L * P * 2) and tuple(logits.shape) == (N, Lq, M * L * P),
-             f"{what}: offsets / logits must be [N,Lq,M*L*P*2] / [N,Lq,M*L*P]")
-    _require(all(t.dtype == torch.float32 for t in (value, reference_points, offsets, logits)), f"{what} is implemented for float32")
-    _require(spatial_shapes.dtype == torch.int64 and level_start_index.dtype == torch.int64,
-             "spatial_shapes and level_start_index must be int64")
-    return N, S, M, D, L, Lq, P, ref_dim
+    name, first, k = rows[0]
+    if level_start_index.shape[0] != L or L <= 0 or M <= 0 or first.dim() != 3 or first.shape[2] % (k * M * L) != 0:
+        raise RuntimeError(f"{what}: level_start_index must be [L] and {name} [N,Lq,{k}*M*L*P]")
+    P = first.shape[2] // (k * M * L)
+    if value.dtype != torch.float32 or reference_points.dtype != torch.float32:
+        raise RuntimeError(f"{what} is implemented for float32")
+    if spatial_shapes.dtype != torch.int64 or level_start_index.dtype != torch.int64:
+        raise RuntimeError("spatial_shapes and level_start_index must be int64")
+    for name, t, k in rows:
+        if t.shape != (N, Lq, k * M * L * P):
+            raise RuntimeError(f"{what}: {name} must be [N,Lq,{k}*M*L*P]")
+        if t.dtype != torch.float32:
+            raise RuntimeError(f"{what} is implemented for float32")
+    _check_inputs([("value", value), ("spatial_shapes", spatial_shapes), ("level_start_index", level_start_index),
+                   ("reference_points", reference_points)])
+    for name, t, _ in rows:
+        if not t.is_cuda or t.device != value.device:
+            raise RuntimeError(f"Not implemented on the CPU ({name} must be a CUDA tensor on {value.device})")
+    return N, S, M, D, L, Lq, P, Lr, ref_dim
+
+
+def _msda_fused_launch(what, value, spatial_shapes, level_start_index, reference_points, ref_dim, Lr,
+                       offsets_ptr, off_pitch, logits_ptr, logit_pitch, N, S, M, D, L, Lq, P):
+    """dfx_msda_fused_forward_f32 on validated operands: offsets and logits as two pointers with their row pitches in
+    floats (two tensors, or two columns of one joint row).  -> [N,Lq,M*D]"""
+    out = torch.empty((N, Lq, M * D), dtype=value.dtype, device=value.device)
+    _call(what, "dfx_msda_fused_forward_f32", value.device,
+          value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(), reference_points.data_ptr(), ref_dim, Lr,
+          offsets_ptr, off_pitch, logits_ptr, logit_pitch, N, S, M, D, L, Lq, P, out.data_ptr())
+    return out
+
+
+def msda_fused_forward(value, spatial_shapes, level_start_index, reference_points, qproj, n_levels, n_points):
+    """softmax + location arithmetic + sampling in one launch (include/dfx_msda.h,
+    dfx_msda_fused_forward_f32).
+
+    value            [N,S,M,D] fp32, contiguous
+    reference_points [N,Lq,Lr,2|4]  (Lr = n_levels, or any Lr over a single value level: the flat read)
+    qproj            [N,Lq,3*M*L*P] = one row per query holding the raw sampling_offsets
+                     Linear output (M*L*P*2 floats) followed by the raw attention_weights
+                     Linear output (M*L*P floats)
+    -> [N,Lq,M*D]
+    """
+    reference_points = reference_points.contiguous()
+    _require(spatial_shapes.shape[0] == n_levels, "spatial_shapes rows must equal n_levels")
+    N, S, M, D, L, Lq, P, Lr, ref_dim = _msda_fused_operands(
+        "msda_fused_forward", value, spatial_shapes, level_start_index, reference_points, (("qproj", qproj, 3),), flat_read=True)
+    _require(P == n_points, "qproj has the wrong shape/dtype")
+    _require(qproj.is_contiguous(), "qproj tensor has to be contiguous")
+    mlp = M * L * P
+    base = qproj.data_ptr()      # both columns of the joint row by address: no tensor views on this path
+    return _msda_fused_launch("msda_fused_forward", value, spatial_shapes, level_start_index, reference_points, ref_dim, Lr,
+                              base, 3 * mlp, base + 2 * mlp * 4, 3 * mlp, N, S, M, D, L, Lq, P)
 
 
 def _msda_fused_forward_split(value, spatial_shapes, level_start_index, reference_points, offsets, logits):
-    """dfx_msda_fused_forward_f32 on offsets and logits as two tensors (two pointers, two row strides); no autograd node."""
-    lib = _lib.load()
-    N, S, M, D, L, Lq, P, ref_dim = _msda_fused_operands("msda_fused", value, spatial_shapes, level_start_index,
-                                                         reference_points, offsets, logits)
+    """The same launch on offsets and logits as two tensors; no autograd node."""
+    N, S, M, D, L, Lq, P, Lr, ref_dim = _msda_fused_operands(
+        "msda_fused", value, spatial_shapes, level_start_index, reference_points, (("offsets", offsets, 2), ("logits", logits, 1)))
     offsets, off_pitch = _pitched_rows(offsets, N, Lq, M * L * P * 2)
     logits, logit_pitch = _pitched_rows(logits, N, Lq, M * L * P)
-    out = torch.empty((N, Lq, M * D), dtype=value.dtype, device=value.device)
-    with _on(value.device):
-        rc = lib.dfx_msda_fused_forward_f32(
-            value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(), reference_points.data_ptr(),
-            ref_dim, L, offsets.data_ptr(), off_pitch, logits.data_ptr(), logit_pitch,
-            N, S, M, D, L, Lq, P, out.data_ptr(), _stream(value.device))
-    _lib.check(rc, "msda_fused")
-    return out
+    return _msda_fused_launch("msda_fused", value, spatial_shapes, level_start_index, reference_points, ref_dim, Lr,
+                              offsets.data_ptr(), off_pitch, logits.data_ptr(), logit_pitch, N, S, M, D, L, Lq, P)
 
 
 def msda_fused_backward(grad_out, value, spatial_shapes, level_start_index, reference_points, offsets, logits,
@@ -281,9 +285,9 @@ def msda_fused_backward(grad_out, value, spatial_shapes, level_start_index, refe
     -> (grad_value [N,S,M,D] | None, grad_offsets like offsets, grad_logits like logits, grad_ref like reference_points | None)
     grad_value is summed with float atomics and is only computed (and its buffer only allocated) with need_value; the
     other three are plain stores: two calls on the same inputs give the same bits."""
-    lib = _lib.load()
-    N, S, M, D, L, Lq, P, ref_dim = _msda_fused_operands("msda_fused_backward", value, spatial_shapes, level_start_index,
-                                                         reference_points, offsets, logits)
+    N, S, M, D, L, Lq, P, _, ref_dim = _msda_fused_operands(
+        "msda_fused_backward", value, spatial_shapes, level_start_index, reference_points,
+        (("offsets", offsets, 2), ("logits", logits, 1)))
     grad_out = grad_out.contiguous()
     _require(grad_out.is_cuda and grad_out.dtype == torch.float32 and grad_out.numel() == N * Lq * M * D,
              "msda_fused_backward: grad_out must be [N,Lq,M*D] fp32 on the GPU")
@@ -294,13 +298,11 @@ def msda_fused_backward(grad_out, value, spatial_shapes, level_start_index, refe
     grad_off = torch.empty((N, Lq, M * L * P * 2), dtype=torch.float32, device=dev)
     grad_logits = torch.empty((N, Lq, M * L * P), dtype=torch.float32, device=dev)
     grad_ref = torch.empty((N, Lq, L, ref_dim), dtype=torch.float32, device=dev) if need_ref else None
-    with _on(dev):
-        rc = lib.dfx_msda_fused_backward_f32(
-            value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(), reference_points.data_ptr(), ref_dim,
-            offsets.data_ptr(), off_pitch, logits.data_ptr(), logit_pitch, grad_out.data_ptr(),
-            N, S, M, D, L, Lq, P, _ptr(grad_value), grad_off.data_ptr(), M * L * P * 2, grad_logits.data_ptr(), M * L * P,
-            _ptr(grad_ref), _stream(dev))
-    _lib.check(rc, "msda_fused_backward")
+    _call("msda_fused_backward", "dfx_msda_fused_backward_f32", dev,
+          value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(), reference_points.data_ptr(), ref_dim,
+          offsets.data_ptr(), off_pitch, logits.data_ptr(), logit_pitch, grad_out.data_ptr(),
+          N, S, M, D, L, Lq, P, _ptr(grad_value), grad_off.data_ptr(), M * L * P * 2, grad_logits.data_ptr(), M * L * P,
+          _ptr(grad_ref))
     return grad_value, grad_off, grad_logits, grad_ref
 
 
@@ -350,6 +352,24 @@ def level_supported(value_like, H, W, Lq, n_heads, head_dim, n_levels, n_points,
             and Lq >= LEVEL_MIN_QUERIES and bool(_lib.load().dfx_msda_fused_level_fits(int(H), int(W))))
 
 
+def _msda_level_launch(what, value, reference_points, qproj, logits_at, layout, N, H, W, out_shape):
+    """dfx_msda_fused_level_forward_f32 (include/dfx_msda.h) on operands whose shapes the caller has checked: `layout` holds
+    their strides, the logits of a query's first head start `logits_at` floats behind its offsets."""
+    Lq, ref_dim = reference_points.shape[1], reference_points.shape[3]
+    out = torch.empty(out_shape, dtype=torch.float32, device=value.device)
+    base = qproj.data_ptr()
+    _call(what, "dfx_msda_fused_level_forward_f32", value.device, value.data_ptr(), reference_points.data_ptr(), ref_dim,
+          base, base + 4 * logits_at, ctypes.byref(layout), N, H, W, Lq, out.data_ptr())
+    return out
+
+
+def _level_reference_points(reference_points, N):
+    reference_points = reference_points.contiguous()
+    _require(reference_points.dim() == 4 and reference_points.shape[0] == N and reference_points.shape[2] == 1
+             and reference_points.dtype == torch.float32, "reference_points must be [N, Lq, 1, 2|4] fp32")
+    return reference_points
+
+
 def msda_level_forward(value_blk, reference_points, qproj_blk, N, H, W):
     """Fused single-level MSDA on operands in the block-major layouts linear(col_block=...) writes and
     linear(x_blocked=True) reads (include/dfx_msda.h, dfx_msda_fused_level_forward_f32):
@@ -360,31 +380,38 @@ def msda_level_forward(value_blk, reference_points, qproj_blk, N, H, W):
                                      head-interleaved sampling_offsets / attention_weights Linear)
     -> [64, N*Lq, 4]  the sampled values, 4-channel chunk k of every query (output_proj's x_blocked operand)
     """
-    import ctypes
-    lib = _lib.load()
-    reference_points = reference_points.contiguous()
+    reference_points = _level_reference_points(reference_points, N)
     _check_inputs([("value_blk", value_blk), ("reference_points", reference_points), ("qproj_blk", qproj_blk)])
-    S = H * W
-    Lq, ref_dim = reference_points.shape[1], reference_points.shape[3]
-    _require(value_blk.shape == (64, N * S, 4) and value_blk.dtype == torch.float32, "value_blk must be [64, N*H*W, 4] fp32")
-    _require(qproj_blk.shape == (8, N * Lq, 12) and qproj_blk.dtype == torch.float32, "qproj_blk must be [8, N*Lq, 12] fp32")
-    _require(reference_points.shape[0] == N and reference_points.shape[2] == 1 and reference_points.dtype == torch.float32,
-             "reference_points must be [N, Lq, 1, 2|4] fp32")
-    out = torch.empty((64, N * Lq, 4), dtype=torch.float32, device=value_blk.device)
-    base = qproj_blk.data_ptr()
-    ns, nq = N * S, N * Lq
-    ly = _lib.LevelLayout(S * 4, 4, 32 * ns, 8 * ns, 4 * ns, 12, 12 * nq, 12, 12 * nq, 4, 32 * nq, 8 * nq, 4 * nq)
-    with _on(value_blk.device):
-        rc = lib.dfx_msda_fused_level_forward_f32(
-            value_blk.data_ptr(), reference_points.data_ptr(), ref_dim, base, base + 32, ctypes.byref(ly),
-            N, H, W, Lq, out.data_ptr(), _stream(value_blk.device))
-    _lib.check(rc, "msda_level_forward")
-    return out
+    Lq = reference_points.shape[1]
+    ns, nq = N * H * W, N * Lq
+    _require(value_blk.shape == (64, ns, 4) and value_blk.dtype == torch.float32, "value_blk must be [64, N*H*W, 4] fp32")
+    _require(qproj_blk.shape == (8, nq, 12) and qproj_blk.dtype == torch.float32, "qproj_blk must be [8, N*Lq, 12] fp32")
+    ly = _lib.LevelLayout(H * W * 4, 4, 32 * ns, 8 * ns, 4 * ns, 12, 12 * nq, 12, 12 * nq, 4, 32 * nq, 8 * nq, 4 * nq)
+    return _msda_level_launch("msda_level_forward", value_blk, reference_points, qproj_blk, 8, ly, N, H, W, (64, nq, 4))
+
+
+def msda_level_forward_reference(value, reference_points, qproj, H, W):
+    """The level-in-LDS kernel on operands in the reference layouts, those of msda_fused_forward with one level.  There it
+    is slower than the wave-per-query kernel (33 vs 26 us at the encoder geometry), so no product path calls it: parity
+    tests and probes do, by this name.  A level that does not fit the CU's LDS raises; no other kernel steps in.
+
+    value [N,H*W,8,32] fp32, reference_points [N,Lq,1,2|4], qproj [N,Lq,96] (64 offsets | 32 logits)  -> [N,Lq,256]
+    """
+    _require(value.dim() == 4 and qproj.dim() == 3, "value must be [N,H*W,8,32], qproj [N,Lq,96]")
+    N = value.shape[0]
+    reference_points = _level_reference_points(reference_points, N)
+    _check_inputs([("value", value), ("reference_points", reference_points), ("qproj", qproj)])
+    Lq, S = reference_points.shape[1], H * W
+    _require(value.shape == (N, S, 8, 32) and value.dtype == torch.float32, "value must be [N, H*W, 8, 32] fp32")
+    _require(qproj.shape == (N, Lq, 96) and qproj.dtype == torch.float32, "qproj must be [N, Lq, 96] fp32")
+    _require(bool(_lib.load().dfx_msda_fused_level_fits(int(H), int(W))),
+             f"msda_level_forward_reference: a {H} x {W} level does not fit the level-in-LDS kernel")
+    ly = _lib.LevelLayout(S * 256, 256, 32, 8, 4, 96, 8, 96, 4, 256, 32, 8, 4)
+    return _msda_level_launch("msda_level_forward_reference", value, reference_points, qproj, 64, ly, N, H, W, (N, Lq, 256))
 
 
 def _roi_align_forward(inp, rois, output_size, spatial_scale, sampling_ratio, aligned, channels_last):
     """The forward entry of include/dfx_roi.h on a float [K,5] contiguous `rois`; no autograd node."""
-    lib = _lib.load()
     ph, pw = (output_size, output_size) if isinstance(output_size, int) else output_size
     _check_inputs([("input", inp), ("rois", rois)])
     _require(inp.dtype == torch.float32, "roi_align is implemented for float32")
@@ -393,15 +420,13 @@ def _roi_align_forward(inp, rois, output_size, spatial_scale, sampling_ratio, al
     if channels_last:
         N, H, W, C = inp.shape
         out = torch.empty((K, ph * pw, C), dtype=inp.dtype, device=inp.device)
-        fn = lib.dfx_roi_align_nhwc_f32
+        fn = "dfx_roi_align_nhwc_f32"
     else:
         N, C, H, W = inp.shape
         out = torch.empty((K, C, ph, pw), dtype=inp.dtype, device=inp.device)
-        fn = lib.dfx_roi_align_nchw_f32
-    with _on(inp.device):
-        rc = fn(inp.data_ptr(), rois.data_ptr(), N, C, H, W, K, ph, pw, float(spatial_scale),
-                int(sampling_ratio), int(bool(aligned)), out.data_ptr(), _stream(inp.device))
-    _lib.check(rc, "roi_align")
+        fn = "dfx_roi_align_nchw_f32"
+    _call("roi_align", fn, inp.device, inp.data_ptr(), rois.data_ptr(), N, C, H, W, K, ph, pw, float(spatial_scale),
+          int(sampling_ratio), int(bool(aligned)), out.data_ptr())
     return out
 
 
@@ -413,7 +438,6 @@ def roi_align_backward(grad_out, rois, input_shape, output_size, spatial_scale, 
     channels_last=True : grad_out [K,ph*pw,C] contiguous -> [N,H,W,C] = input_shape
     The library zero-fills the fresh result and accumulates into it with fp32 atomics.
     """
-    lib = _lib.load()
     ph, pw = (output_size, output_size) if isinstance(output_size, int) else output_size
     rois = rois.contiguous().float()
     _check_inputs([("grad_output", grad_out), ("rois", rois)])
@@ -423,16 +447,14 @@ def roi_align_backward(grad_out, rois, input_shape, output_size, spatial_scale, 
     K = rois.shape[0]
     if channels_last:
         N, H, W, C = input_shape
-        want, fn = (K, ph * pw, C), lib.dfx_roi_align_backward_nhwc_f32
+        want, fn = (K, ph * pw, C), "dfx_roi_align_backward_nhwc_f32"
     else:
         N, C, H, W = input_shape
-        want, fn = (K, C, ph, pw), lib.dfx_roi_align_backward_nchw_f32
+        want, fn = (K, C, ph, pw), "dfx_roi_align_backward_nchw_f32"
     _require(tuple(grad_out.shape) == want, f"grad_output must be {want}, got {tuple(grad_out.shape)}")
     grad_input = torch.empty(tuple(input_shape), dtype=grad_out.dtype, device=grad_out.device)
-    with _on(grad_out.device):
-        rc = fn(grad_out.data_ptr(), rois.data_ptr(), N, C, H, W, K, ph, pw, float(spatial_scale),
-                int(sampling_ratio), int(bool(aligned)), grad_input.data_ptr(), _stream(grad_out.device))
-    _lib.check(rc, "roi_align_backward")
+    _call("roi_align_backward", fn, grad_out.device, grad_out.data_ptr(), rois.data_ptr(), N, C, H, W, K, ph, pw,
+          float(spatial_scale), int(sampling_ratio), int(bool(aligned)), grad_input.data_ptr())
     return grad_input
 
 
@@ -474,7 +496,6 @@ def bias_act_(x, bias, residual=None, relu=True):
     """In place on ``x`` [N,C,*spatial] (contiguous NCHW): x = relu?(x + bias[c] (+ residual)).
     One HBM pass for what the reference runs as FrozenBatchNorm2d (after folding its scale into
     the convolution weights) + residual add + ReLU (include/dfx_fused.h)."""
-    lib = _lib.load()
     named = [("x", x), ("bias", bias)] + ([("residual", residual)] if residual is not None else [])
     _check_inputs(named)
     _require(x.dtype == torch.float32 and bias.dtype == torch.float32, "bias_act_ is implemented for float32")
@@ -483,10 +504,8 @@ def bias_act_(x, bias, residual=None, relu=True):
     if residual is not None:
         _require(residual.shape == x.shape and residual.dtype == x.dtype, "residual must match x")
     hw = x.numel() // max(N * C, 1)
-    with _on(x.device):
-        rc = lib.dfx_bias_act_nchw_f32(x.data_ptr(), bias.data_ptr(), 0 if residual is None else residual.data_ptr(),
-                                       x.data_ptr(), N, C, hw, int(bool(relu)), _stream(x.device))
-    _lib.check(rc, "bias_act_")
+    _call("bias_act_", "dfx_bias_act_nchw_f32", x.device, x.data_ptr(), bias.data_ptr(), _ptr(residual), x.data_ptr(),
+          N, C, hw, int(bool(relu)))
     return x
 
 
@@ -530,7 +549,6 @@ def linear(x, weight, bias=None, relu=False, residual=None, add=None, row_mask=N
     col_block = w > 0 stores the result column-block-major instead: [N / w, rows, w] (the layout
     msda_level_forward reads), N a multiple of w.  x_blocked: x is K-block-major [K/4, rows, 4] (the
     layout msda_level_forward writes); the result is then [rows, N]."""
-    lib = _lib.load()
     N = weight.shape[0]
     if x_blocked:
         _require(x.dim() == 3 and x.shape[2] == 4 and add is None, "x_blocked: x must be [K/4, rows, 4], no add")
@@ -573,37 +591,33 @@ def linear(x, weight, bias=None, relu=False, residual=None, add=None, row_mask=N
         y = linear(x, weight, bias, add=add, x_blocked=x_blocked, act=act, relu=relu)
         return add_layernorm(y, None if residual is None else residual.reshape(y.shape), norm)
     splits = _split_k(M, N, K) if (add is None and row_mask is None and not col_block and not x_blocked and N % 4 == 0) else 0
+    if splits > 1:
+        ws = torch.empty((splits, M, N), dtype=torch.float32, device=x.device)
+        _call("linear (split-K)", "dfx_gemm_splitk_f32", x.device, x2.data_ptr(), K, weight.data_ptr(), K, 0, _ptr(bias), 0,
+              _ptr(residual), N, out.data_ptr(), N, M, N, K, code, splits, ws.data_ptr())
+        return out
+    # The kernel addresses an operand with 32-bit byte offsets (buffer loads): A, and the residual, must stay below
+    # 2 GiB per call.  More rows than that (long clips of multi-scale token maps) go through in row ranges; every
+    # layout here is row-separable (strides are explicit arguments), so a range is the same call on offset pointers.
+    rows_max = (_GEMM_MAX_BYTES - 1) // (4 * max(K, N if residual is not None else 1))
+    if x_blocked:
+        _require(M * K * 4 < _GEMM_MAX_BYTES, "linear: a K-block-major x of 2 GiB or more is not supported")
+        rows_max = M
+    rows_max = max(128, rows_max // 128 * 128)
+    out_row = int(col_block) if col_block else N            # elements a row advances the output pointer by
     with _on(x.device):
-        if splits > 1:
-            ws = torch.empty((splits, M, N), dtype=torch.float32, device=x.device)
-            rc = lib.dfx_gemm_splitk_f32(x2.data_ptr(), K, weight.data_ptr(), K, 0, _ptr(bias), 0, _ptr(residual), N,
-                                         out.data_ptr(), N, M, N, K, code, splits, ws.data_ptr(), _stream(x.device))
-            _lib.check(rc, "linear (split-K)")
-            return out
-        # The kernel addresses an operand with 32-bit byte offsets (buffer loads): A, and the residual, must stay below
-        # 2 GiB per call.  More rows than that (long clips of multi-scale token maps) go through in row ranges; every
-        # layout here is row-separable (strides are explicit arguments), so a range is the same call on offset pointers.
-        rows_max = (_GEMM_MAX_BYTES - 1) // (4 * max(K, N if residual is not None else 1))
-        if x_blocked:
-            _require(M * K * 4 < _GEMM_MAX_BYTES, "linear: a K-block-major x of 2 GiB or more is not supported")
-            rows_max = M
-        rows_max = max(128, rows_max // 128 * 128)
-        out_row = int(col_block) if col_block else N            # elements a row advances the output pointer by
         for r0 in range(0, M, rows_max):
             r1 = min(M, r0 + rows_max)
             off = lambda t, per_row: 0 if t is None else t.data_ptr() + r0 * per_row * t.element_size()  # noqa: E731
-            rc = lib.dfx_gemm_f32(off(x2, 4 if x_blocked else K), off(add, K), K, 0, weight.data_ptr(), K, 0, 0, _ptr(bias), 0,
-                                  off(residual, N), N, 0, off(row_mask, 1), 0, off(out, out_row), N, 0, r1 - r0, N, K, 1,
-                                  code, int(col_block), M * int(col_block), M * 4 if x_blocked else 0,
-                                  _stream(x.device))
-            _lib.check(rc, "linear")
+            _call("linear", "dfx_gemm_f32", x.device, off(x2, 4 if x_blocked else K), off(add, K), K, 0, weight.data_ptr(), K, 0, 0,
+                  _ptr(bias), 0, off(residual, N), N, 0, off(row_mask, 1), 0, off(out, out_row), N, 0, r1 - r0, N, K, 1,
+                  code, int(col_block), M * int(col_block), M * 4 if x_blocked else 0)
     return out
 
 
 def conv1x1(x, weight, bias=None, residual=None, relu=False, stride=1):
     """1x1 convolution on NCHW as a batched GEMM W[Co,Ci] x X_n[Ci,HW] with the folded-BN bias,
     the residual add and ReLU fused into the epilogue.  x [N,Ci,H,W], weight [Co,Ci(,1,1)]."""
-    lib = _lib.load()
     if stride != 1:
         x = x[:, :, ::stride, ::stride].contiguous()
     Nb, Ci, H, W = x.shape
@@ -617,11 +631,8 @@ def conv1x1(x, weight, bias=None, residual=None, relu=False, stride=1):
     out = torch.empty((Nb, Co, H, W), dtype=x.dtype, device=x.device)
     if residual is not None:
         _require(residual.shape == out.shape, "residual must match the output")
-    with _on(x.device):
-        rc = lib.dfx_gemm_f32(w2.data_ptr(), 0, Ci, 0, x.data_ptr(), HW, Ci * HW, 1, _ptr(bias), 1,
-                              _ptr(residual), HW, Co * HW, 0, 0, out.data_ptr(), HW, Co * HW, Co, HW, Ci, Nb,
-                              int(bool(relu)), 0, 0, 0, _stream(x.device))
-    _lib.check(rc, "conv1x1")
+    _call("conv1x1", "dfx_gemm_f32", x.device, w2.data_ptr(), 0, Ci, 0, x.data_ptr(), HW, Ci * HW, 1, _ptr(bias), 1,
+          _ptr(residual), HW, Co * HW, 0, 0, out.data_ptr(), HW, Co * HW, Co, HW, Ci, Nb, int(bool(relu)), 0, 0, 0)
     return out
 
 
@@ -629,7 +640,6 @@ def conv1x1_pair(x1, x2, weight, bias=None, relu=False):
     """relu?(weight x [x1 ; x2] + bias): two NCHW inputs of one map size concatenated along the channels inside the
     product (include/dfx_gemm.h, dfx_conv1x1_pair_f32) - a bottleneck's last 1x1 convolution and its stride-1
     projection shortcut in one GEMM.  x1 [N,K1,H,W], x2 [N,K2,H,W], weight [Co,K1+K2] -> [N,Co,H,W]."""
-    lib = _lib.load()
     _check_inputs([("x1", x1), ("x2", x2), ("weight", weight)] + ([("bias", bias)] if bias is not None else []))
     Nb, K1, H, W = x1.shape
     K2 = x2.shape[1]
@@ -637,11 +647,8 @@ def conv1x1_pair(x1, x2, weight, bias=None, relu=False):
     _require(x1.dtype == torch.float32 and x2.shape == (Nb, K2, H, W) and weight.shape == (Co, K1 + K2),
              "conv1x1_pair: x1 [N,K1,H,W], x2 [N,K2,H,W], weight [Co,K1+K2], fp32")
     out = torch.empty((Nb, Co, H, W), dtype=x1.dtype, device=x1.device)
-    with _on(x1.device):
-        rc = lib.dfx_conv1x1_pair_f32(weight.data_ptr(), x1.data_ptr(), K1 * H * W, K1, x2.data_ptr(), K2 * H * W, K2,
-                                      _ptr(bias), out.data_ptr(), Co * H * W, Co, H * W, Nb, int(bool(relu)),
-                                      _stream(x1.device))
-    _lib.check(rc, "conv1x1_pair")
+    _call("conv1x1_pair", "dfx_conv1x1_pair_f32", x1.device, weight.data_ptr(), x1.data_ptr(), K1 * H * W, K1, x2.data_ptr(),
+          K2 * H * W, K2, _ptr(bias), out.data_ptr(), Co * H * W, Co, H * W, Nb, int(bool(relu)))
     return out
 
 
@@ -659,7 +666,6 @@ def conv1x1_chain(x, w3, b3, w1, b1, residual=None, x2=None, relu_z=True):
     x [N,K1,H,W], x2 [N,K2,H,W] or None, w3 [Co,K1+K2], w1 [C1,Co], residual [N,Co,H,W] or None.
     A shape the fused kernel does not cover runs as the two separate launches (conv1x1 / conv1x1_pair, then conv1x1):
     the results are the same bit for bit."""
-    lib = _lib.load()
     Nb, K1, H, W = x.shape
     K2 = 0 if x2 is None else x2.shape[1]
     Co, C1, HW = w3.shape[0], w1.shape[0], H * W
@@ -677,11 +683,9 @@ def conv1x1_chain(x, w3, b3, w1, b1, residual=None, x2=None, relu_z=True):
         return y, conv1x1(y, w1, b1, relu=relu_z)
     y = torch.empty((Nb, Co, H, W), dtype=x.dtype, device=x.device)
     z = torch.empty((Nb, C1, H, W), dtype=x.dtype, device=x.device)
-    with _on(x.device):
-        rc = lib.dfx_conv1x1_chain_f32(w3.data_ptr(), x.data_ptr(), K1 * HW, K1, _ptr(x2), K2 * HW, K2, _ptr(b3),
-                                       _ptr(residual), Co * HW, y.data_ptr(), Co * HW, w1.data_ptr(), _ptr(b1),
-                                       z.data_ptr(), C1 * HW, Co, C1, HW, Nb, int(bool(relu_z)), _stream(x.device))
-    _lib.check(rc, "conv1x1_chain")
+    _call("conv1x1_chain", "dfx_conv1x1_chain_f32", x.device, w3.data_ptr(), x.data_ptr(), K1 * HW, K1, _ptr(x2), K2 * HW, K2,
+          _ptr(b3), _ptr(residual), Co * HW, y.data_ptr(), Co * HW, w1.data_ptr(), _ptr(b1), z.data_ptr(), C1 * HW, Co, C1, HW,
+          Nb, int(bool(relu_z)))
     return y, z
 
 
@@ -698,14 +702,11 @@ def _dynamic_conv_checks(feats, params, norm1, norm2):
 
 def _dynamic_conv_forward(feats, params, norm1, norm2):
     """The forward entry of include/dfx_roi.h (dfx_dynamic_conv_f32); no autograd node."""
-    lib = _lib.load()
     K, R, C, dd = _dynamic_conv_checks(feats, params, norm1, norm2)
     out = torch.empty_like(feats)
-    with _on(feats.device):
-        rc = lib.dfx_dynamic_conv_f32(feats.data_ptr(), params.data_ptr(), params.stride(0), norm1.weight.data_ptr(),
-                                      norm1.bias.data_ptr(), norm2.weight.data_ptr(), norm2.bias.data_ptr(),
-                                      out.data_ptr(), K, R, C, dd, float(norm1.eps), _stream(feats.device))
-    _lib.check(rc, "dynamic_conv")
+    _call("dynamic_conv", "dfx_dynamic_conv_f32", feats.device, feats.data_ptr(), params.data_ptr(), params.stride(0),
+          norm1.weight.data_ptr(), norm1.bias.data_ptr(), norm2.weight.data_ptr(), norm2.bias.data_ptr(), out.data_ptr(),
+          K, R, C, dd, float(norm1.eps))
     return out
 
 
@@ -718,7 +719,6 @@ def dynamic_conv_backward(grad_out, feats, params, norm1, norm2, need_feats=True
     -> (grad_feats [K,R,256] | None, grad_params like params (zeros beyond column 2*C*dd) | None,
         grad_norm1_weight, grad_norm1_bias, grad_norm2_weight, grad_norm2_bias)
     No atomics: two calls on the same inputs give the same bits."""
-    lib = _lib.load()
     K, R, C, dd = _dynamic_conv_checks(feats, params, norm1, norm2)
     _check_inputs([("grad_out", grad_out)])
     _require(grad_out.shape == feats.shape and grad_out.dtype == torch.float32 and grad_out.device == feats.device,
@@ -731,12 +731,10 @@ def dynamic_conv_backward(grad_out, feats, params, norm1, norm2, need_feats=True
         grad_params = (torch.empty if width == 2 * C * dd else torch.zeros)((K, pitch), dtype=torch.float32, device=feats.device)
     grad_ln = torch.empty(2 * dd + 2 * C, dtype=torch.float32, device=feats.device)
     ws = torch.empty(DYNCONV_BWD_WS_FLOATS, dtype=torch.float32, device=feats.device)
-    with _on(feats.device):
-        rc = lib.dfx_dynamic_conv_backward_f32(
-            grad_out.data_ptr(), feats.data_ptr(), params.data_ptr(), params.stride(0), norm1.weight.data_ptr(),
-            norm1.bias.data_ptr(), norm2.weight.data_ptr(), norm2.bias.data_ptr(), _ptr(grad_feats), _ptr(grad_params), pitch,
-            grad_ln.data_ptr(), ws.data_ptr(), K, R, C, dd, float(norm1.eps), _stream(feats.device))
-    _lib.check(rc, "dynamic_conv_backward")
+    _call("dynamic_conv_backward", "dfx_dynamic_conv_backward_f32", feats.device,
+          grad_out.data_ptr(), feats.data_ptr(), params.data_ptr(), params.stride(0), norm1.weight.data_ptr(),
+          norm1.bias.data_ptr(), norm2.weight.data_ptr(), norm2.bias.data_ptr(), _ptr(grad_feats), _ptr(grad_params), pitch,
+          grad_ln.data_ptr(), ws.data_ptr(), K, R, C, dd, float(norm1.eps))
     dg1, db1, dg2, db2 = grad_ln.split([dd, dd, C, C])
     if grad_params is not None and pitch != width:
         grad_params = grad_params[:, :width]
@@ -786,7 +784,6 @@ def dynamic_conv(feats, params, norm1, norm2):
 def mha(q, k, v, heads, scale):
     """softmax(scale * q k^T) v per head (include/dfx_mha.h): q [B,Lq,E], k / v [B,Lk,E], E = 32*heads, fp32.
     The tensors may be column slices of a joint projection (last dimension contiguous).  -> [B,Lq,E]"""
-    lib = _lib.load()
     for nm, t in (("q", q), ("k", k), ("v", v)):
         if not t.is_cuda:
             raise RuntimeError(f"{nm} must be a CUDA tensor (the fused attention has no CPU path)")
@@ -796,18 +793,14 @@ def mha(q, k, v, heads, scale):
     Lk = k.shape[1]
     _require(k.shape == (B, Lk, E) and v.shape == (B, Lk, E), "mha: k and v must be [B,Lk,E]")
     out = torch.empty((B, Lq, E), dtype=torch.float32, device=q.device)
-    with _on(q.device):
-        rc = lib.dfx_mha_f32(q.data_ptr(), q.stride(0), q.stride(1), k.data_ptr(), k.stride(0), k.stride(1),
-                             v.data_ptr(), v.stride(0), v.stride(1), out.data_ptr(), Lq * E, E, B, heads, Lq, Lk,
-                             float(scale), _stream(q.device))
-    _lib.check(rc, "mha")
+    _call("mha", "dfx_mha_f32", q.device, q.data_ptr(), q.stride(0), q.stride(1), k.data_ptr(), k.stride(0), k.stride(1),
+          v.data_ptr(), v.stride(0), v.stride(1), out.data_ptr(), Lq * E, E, B, heads, Lq, Lk, float(scale))
     return out
 
 
 def box_refine(delta, reference, eps=1e-5):
     """sigmoid(delta + inverse_sigmoid(reference)) on the first reference.shape[-1] (2 or 4) of the 4 box
     columns, sigmoid(delta) on the others, in one launch (include/dfx_fused.h).  delta [...,4]."""
-    lib = _lib.load()
     delta, reference = delta.contiguous(), reference.contiguous()
     _check_inputs([("delta", delta), ("reference", reference)])
     rd = reference.shape[-1]
@@ -815,17 +808,14 @@ def box_refine(delta, reference, eps=1e-5):
              and delta.dtype == torch.float32 and reference.dtype == torch.float32,
              "box_refine: delta [...,4], reference [...,2|4], fp32")
     out = torch.empty_like(delta)
-    with _on(delta.device):
-        rc = lib.dfx_box_refine_f32(delta.data_ptr(), reference.data_ptr(), rd, out.data_ptr(), delta.numel() // 4,
-                                    float(eps), _stream(delta.device))
-    _lib.check(rc, "box_refine")
+    _call("box_refine", "dfx_box_refine_f32", delta.device, delta.data_ptr(), reference.data_ptr(), rd, out.data_ptr(),
+          delta.numel() // 4, float(eps))
     return out
 
 
 def add_layernorm(x, residual, norm):
     """``norm(x + residual)`` for an nn.LayerNorm over the last dimension, in one pass
     (include/dfx_fused.h); residual may be None."""
-    lib = _lib.load()
     C = x.shape[-1]
     x2 = x.contiguous()
     named = [("x", x2), ("weight", norm.weight), ("bias", norm.bias)]
@@ -836,26 +826,20 @@ def add_layernorm(x, residual, norm):
     _check_inputs(named)
     _require(x2.dtype == torch.float32 and norm.weight.numel() == C, "add_layernorm: fp32, LayerNorm over the last dim")
     out = torch.empty_like(x2)
-    with _on(x2.device):
-        rc = lib.dfx_add_layernorm_f32(x2.data_ptr(), _ptr(residual), norm.weight.data_ptr(), norm.bias.data_ptr(),
-                                       out.data_ptr(), x2.numel() // C, C, float(norm.eps), _stream(x2.device))
-    _lib.check(rc, "add_layernorm")
+    _call("add_layernorm", "dfx_add_layernorm_f32", x2.device, x2.data_ptr(), _ptr(residual), norm.weight.data_ptr(),
+          norm.bias.data_ptr(), out.data_ptr(), x2.numel() // C, C, float(norm.eps))
     return out
 
 
 def bias_relu_maxpool(x, bias):
     """maxpool3x3/s2/p1(relu(x + bias[c])) on NCHW in one pass: the ResNet stem's epilogue
     (include/dfx_fused.h)."""
-    lib = _lib.load()
     _check_inputs([("x", x), ("bias", bias)])
     _require(x.dtype == torch.float32 and x.dim() == 4 and bias.numel() == x.shape[1], "bias_relu_maxpool: fp32 NCHW")
     N, C, H, W = x.shape
     out = torch.empty((N, C, (H + 1) // 2, (W + 1) // 2), dtype=x.dtype, device=x.device)
-    with _on(x.device):
-        rc = lib.dfx_bias_relu_maxpool_f32(x.data_ptr(), bias.data_ptr(), out.data_ptr(), N, C, H, W, _stream(x.device))
-    _lib.check(rc, "bias_relu_maxpool")
+    _call("bias_relu_maxpool", "dfx_bias_relu_maxpool_f32", x.device, x.data_ptr(), bias.data_ptr(), out.data_ptr(), N, C, H, W)
     return out
-
 
 
 class ConvPlan:
@@ -884,8 +868,7 @@ class ConvPlan:
         self.stride, self.padding, self.dilation, self.act = int(stride), int(padding), int(dilation), ACT[act]
         self.bias = None if bias is None else bias.detach().float().contiguous()
         wino_ok = kh == 3 and kw == 3 and stride == 1 and padding == dilation and Ci % 8 == 0 and Co % 64 == 0
-        lib = _lib.load()
-        tile_ok = bool(lib.dfx_conv2d_tile_fits(Ci, Co, kh, kw, int(stride), int(dilation)))
+        tile_ok = bool(_lib.load().dfx_conv2d_tile_fits(Ci, Co, kh, kw, int(stride), int(dilation)))
         self.algo = algo or ("wino" if wino_ok else "tile" if (tile_ok and Ci <= 4 and USE_TILE_CONV) else "igemm")
         _require(self.algo != "wino" or wino_ok, "ConvPlan: geometry not covered by the Winograd kernel")
         _require(self.algo != "tile" or tile_ok, "ConvPlan: geometry not covered by the tile kernel")
@@ -893,9 +876,7 @@ class ConvPlan:
         if self.algo == "wino":
             self.u = torch.empty(16 * Co * Ci, dtype=torch.float32, device=w.device)
             sc = None if scale is None else scale.detach().float().contiguous()
-            with _on(w.device):
-                rc = lib.dfx_wino_weights_f32(w.data_ptr(), _ptr(sc), self.u.data_ptr(), Co, Ci, _stream(w.device))
-            _lib.check(rc, "wino_weights")
+            _call("wino_weights", "dfx_wino_weights_f32", w.device, w.data_ptr(), _ptr(sc), self.u.data_ptr(), Co, Ci)
         else:
             if scale is not None:
                 w = w * scale.detach().reshape(-1, 1, 1, 1)
@@ -923,7 +904,6 @@ class ConvPlan:
         return (H + 2 * self.padding - eff_h) // self.stride + 1, (W + 2 * self.padding - eff_w) // self.stride + 1
 
     def __call__(self, x):
-        lib = _lib.load()
         _require(x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == self.Ci,
                  "conv: x must be a CUDA fp32 tensor [N,Ci,H,W] (no CPU path)")
         N, _, H, W = x.shape
@@ -945,18 +925,16 @@ class ConvPlan:
                 n1 = min(N, n0 + step)
                 xs, ys = x[n0:n1], y[n0:n1]
                 if self.algo == "wino":
-                    rc = lib.dfx_conv3x3_wino_f32(xs.data_ptr(), self.u.data_ptr(), _ptr(self.bias), ys.data_ptr(), n1 - n0, self.Ci,
-                                                  H, W, self.Co, self.dilation, self.act, _stream(x.device))
+                    _call("conv wino", "dfx_conv3x3_wino_f32", x.device, xs.data_ptr(), self.u.data_ptr(), _ptr(self.bias),
+                          ys.data_ptr(), n1 - n0, self.Ci, H, W, self.Co, self.dilation, self.act)
                 elif self.algo == "tile":
-                    rc = lib.dfx_conv2d_tile_f32(xs.data_ptr(), self.wp.data_ptr(), _ptr(self.bias), ys.data_ptr(), n1 - n0, self.Ci,
-                                                 H, W, self.Co, Ho, Wo, self.Kpad, self.kh, self.kw, self.stride, self.padding,
-                                                 self.act, image_stride, _stream(x.device))
+                    _call("conv tile", "dfx_conv2d_tile_f32", x.device, xs.data_ptr(), self.wp.data_ptr(), _ptr(self.bias),
+                          ys.data_ptr(), n1 - n0, self.Ci, H, W, self.Co, Ho, Wo, self.Kpad, self.kh, self.kw, self.stride,
+                          self.padding, self.act, image_stride)
                 else:
-                    rc = lib.dfx_conv2d_igemm_f32(xs.data_ptr(), self.wp.data_ptr(), self._ktab(H, W, x.device).data_ptr(),
-                                                  _ptr(self.bias), ys.data_ptr(), n1 - n0, self.Ci, H, W, self.Co, Ho, Wo, self.Kpad,
-                                                  self.kh, self.kw, self.stride, self.padding, self.dilation, self.act,
-                                                  image_stride, _stream(x.device))
-                _lib.check(rc, "conv " + self.algo)
+                    _call("conv igemm", "dfx_conv2d_igemm_f32", x.device, xs.data_ptr(), self.wp.data_ptr(),
+                          self._ktab(H, W, x.device).data_ptr(), _ptr(self.bias), ys.data_ptr(), n1 - n0, self.Ci, H, W, self.Co,
+                          Ho, Wo, self.Kpad, self.kh, self.kw, self.stride, self.padding, self.dilation, self.act, image_stride)
         return y
 
 
@@ -965,15 +943,11 @@ def group_norm(x, norm, tokens_out=False):
     (include/dfx_fused.h, dfx_group_norm_f32).  tokens_out: the result is written token-major [N,H*W,C] and
     returned as an NCHW-shaped VIEW of that memory, so ``y.flatten(2).transpose(1, 2)`` - what the transformer
     does next - is already contiguous and costs nothing."""
-    lib = _lib.load()
     _check_inputs([("x", x), ("weight", norm.weight), ("bias", norm.bias)])
     _require(x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == norm.num_channels, "group_norm: fp32 NCHW")
     N, C, H, W = x.shape
     stats = torch.empty(N * norm.num_groups * 2, dtype=torch.float32, device=x.device)
     y = torch.empty((N, H * W, C) if tokens_out else (N, C, H, W), dtype=torch.float32, device=x.device)
-    with _on(x.device):
-        rc = lib.dfx_group_norm_f32(x.data_ptr(), norm.weight.data_ptr(), norm.bias.data_ptr(), stats.data_ptr(),
-                                    y.data_ptr(), N, C, H * W, norm.num_groups, float(norm.eps), int(bool(tokens_out)),
-                                    _stream(x.device))
-    _lib.check(rc, "group_norm")
+    _call("group_norm", "dfx_group_norm_f32", x.device, x.data_ptr(), norm.weight.data_ptr(), norm.bias.data_ptr(),
+          stats.data_ptr(), y.data_ptr(), N, C, H * W, norm.num_groups, float(norm.eps), int(bool(tokens_out)))
     return y.transpose(1, 2).unflatten(2, (H, W)) if tokens_out else y

@@ -3,16 +3,19 @@
 
 Same constructor, parameter names (``sampling_offsets``, ``attention_weights``,
 ``value_proj``, ``output_proj`` -> same state_dict keys), initialisation and forward
-signature as the reference.  Three execution routes:
+signature as the reference.  Four execution routes, the first that applies:
 
-* inference on the GPU with the production head geometry (8 heads x 32 channels, 4 points,
+* "level": inference on the GPU, fp32, one level that fits a CU's LDS under many queries (encoder, depth fusion) with the
+  host sizes riding on the shapes tensor: the level-in-LDS kernel (csrc/msda_level.hip) between projections that exchange
+  block-major operands with it (``dfx.ops.level_supported``);
+* "fused": inference on the GPU with the production head geometry (8 heads x 32 channels, 4 points,
   <= 4 levels, fp32): ONE GEMM produces [offsets | logits] per query and the fused kernel
   (csrc/msda_fused.hip) does softmax, location arithmetic and sampling in one launch;
-* training (grad mode) on the GPU with the same geometry, fp32, no autocast and one reference level
+* "train": training (grad mode) on the GPU with the same geometry, fp32, no autocast and one reference level
   per value level: the four Linear layers under autograd, and between them the same fused kernel
   with the fused backward (csrc/msda_fused_backward.hip) behind it (``dfx.ops.msda_fused``);
-* anything else (fp64, autocast, odd geometry, the temporal decoder's flat read in grad mode): the
-  reference's op sequence with the autograd operator ``MSDeformAttnFunction``
+* "operator": anything else (fp64, autocast, odd geometry, the temporal decoder's flat read in grad mode, DFX_MSDA_TRAIN=0):
+  the reference's op sequence with the autograd operator ``MSDeformAttnFunction``
   (csrc/msda_forward.hip / msda_backward.hip).
 
 There is no CPU route: like the reference's op (ms_deform_attn.h:38) it raises on CPU tensors.
@@ -103,6 +106,42 @@ class MSDeformAttn(nn.Module):
             self._qproj_head_key = self._qproj_cache[0]
         return self._qproj_head
 
+    def _route(self, q_parts, reference_points, input_flatten, value, host):
+        """Which kernels run this call: "level", "fused", "train" or "operator" (the module docstring, in that order)."""
+        M, L, P = self.n_heads, self.n_levels, self.n_points
+        D, Lq, Lr = self.d_model // M, q_parts[0].shape[1], reference_points.shape[2]
+        no_grad = not torch.is_grad_enabled() or not (any(t.requires_grad for t in q_parts) or input_flatten.requires_grad)
+        if no_grad and input_flatten.is_cuda and input_flatten.dtype == torch.float32 \
+                and _ops.fused_supported(input_flatten, M, D, L, P, Lr):
+            if host is not None and _ops.level_supported(input_flatten, host[0][0], host[0][1], Lq, M, D, L, P, Lr):
+                return "level"
+            return "fused"
+        v = input_flatten if value is None else value          # (value_proj keeps device and, outside autocast, dtype)
+        q_dtype = torch.promote_types(q_parts[0].dtype, q_parts[-1].dtype)            # of the summed (src, pos) pair
+        if (MSDA_TRAIN and v.is_cuda and not torch.is_autocast_enabled() and Lr == L
+                and v.dtype == q_dtype == reference_points.dtype == torch.float32 and _ops.fused_supported(v, M, D, L, P, Lr)):
+            return "train"
+        return "operator"
+
+    def _project_values(self, input_flatten, input_padding_mask, kernel, col_block=0):
+        """value_proj with the padded tokens zeroed: one GEMM launch with the mask in its epilogue (``kernel``), else the
+        Linear module and a masked_fill."""
+        if kernel:
+            return _ops.linear(input_flatten.contiguous(), self.value_proj.weight, self.value_proj.bias,
+                               row_mask=input_padding_mask, col_block=col_block)
+        value = self.value_proj(input_flatten)
+        return value if input_padding_mask is None else value.masked_fill(input_padding_mask[..., None], float(0))
+
+    def _project_output(self, sampled, post, N, Lq, fuse_post=False, blocked=False):
+        """output_proj and ``post`` on the sampled values, [N,Lq,C] or (``blocked``) the level kernel's [C/4, N*Lq, 4];
+        fuse_post: the add and the LayerNorm of a fusable post ride behind the GEMM (dfx.ops.linear(norm=...))."""
+        proj = self.output_proj
+        if fuse_post and post_is_fusable(post) and self.d_model == 256:
+            out = _ops.linear(sampled, proj.weight, proj.bias, x_blocked=blocked, residual=post[0].contiguous(), norm=post[1])
+            return out.view(N, Lq, -1) if blocked else out
+        out = _ops.linear(sampled, proj.weight, proj.bias, x_blocked=True).view(N, Lq, -1) if blocked else proj(sampled)
+        return apply_post(post, out)
+
     def forward(self, query, reference_points, input_flatten, input_spatial_shapes, input_level_start_index,
                 input_padding_mask=None, post=None, value=None):
         """query [N,Lq,C] (or a (tensor, positional_embedding) pair whose sum is the query: the add is
@@ -115,7 +154,8 @@ class MSDeformAttn(nn.Module):
         value [N,S,C]: ``value_proj(input_flatten)`` with the padded tokens already zeroed, when the caller projected the
         values of several layers that share ``input_flatten`` in one launch (``project_values``); the single-level
         many-query route (block-major operands) ignores it."""
-        N, Lq, _ = (query[0] if isinstance(query, tuple) else query).shape
+        q_parts = query if isinstance(query, tuple) else (query,)
+        N, Lq, _ = q_parts[0].shape
         _, S, _ = input_flatten.shape
         M, L, P = self.n_heads, self.n_levels, self.n_points
         D = self.d_model // M
@@ -127,60 +167,37 @@ class MSDeformAttn(nn.Module):
         if ref_dim not in (2, 4):
             raise ValueError(f"Last dim of reference_points must be 2 or 4, but get {ref_dim} instead.")
 
-        q_parts = query if isinstance(query, tuple) else (query,)
-        no_grad = not torch.is_grad_enabled() or not (any(t.requires_grad for t in q_parts) or input_flatten.requires_grad)
-        fused = no_grad and input_flatten.is_cuda and input_flatten.dtype == torch.float32 \
-            and _ops.fused_supported(input_flatten, M, D, L, P, reference_points.shape[2])
         host = getattr(input_spatial_shapes, "_dfx_host", None)
-        if fused and host is not None and _ops.level_supported(input_flatten, host[0][0], host[0][1], Lq, M, D, L, P,
-                                                               reference_points.shape[2]):
-            # single-level attention over many queries (encoder, depth fusion): the level lives in LDS and
-            # the three projections exchange block-major operands with the kernel (include/dfx_msda.h)
-            q, q_add = query if isinstance(query, tuple) else (query, None)
-            w, b = self._qproj_params_by_head()
-            value = _ops.linear(input_flatten.contiguous(), self.value_proj.weight, self.value_proj.bias,
-                                row_mask=input_padding_mask, col_block=4)
-            qproj = _ops.linear(q.contiguous(), w, b, add=None if q_add is None else q_add.contiguous(), col_block=12)
-            sampled = _ops.msda_level_forward(value, reference_points, qproj, N, host[0][0], host[0][1])
-            if post_is_fusable(post) and self.d_model == 256:
-                return _ops.linear(sampled, self.output_proj.weight, self.output_proj.bias, x_blocked=True,
-                                   residual=post[0].contiguous(), norm=post[1]).view(N, Lq, -1)
-            out = _ops.linear(sampled, self.output_proj.weight, self.output_proj.bias, x_blocked=True).view(N, Lq, -1)
-            return apply_post(post, out)
-        if fused:
-            # value_proj (+ masked_fill of padded tokens), [offsets | logits] in one GEMM (+ the
-            # caller's ``src + pos`` add when handed over as a (src, pos) pair), fused sampling
-            q, q_add = query if isinstance(query, tuple) else (query, None)
-            w, b = self._qproj_params()
-            if value is None:
-                value = _ops.linear(input_flatten.contiguous(), self.value_proj.weight, self.value_proj.bias,
-                                    row_mask=input_padding_mask)
-            qproj = _ops.linear(q.contiguous(), w, b, add=None if q_add is None else q_add.contiguous())
-            sampled = _ops.msda_fused_forward(value.view(N, S, M, D), input_spatial_shapes, input_level_start_index,
-                                              reference_points, qproj, L, P)
-            if post_is_fusable(post) and self.d_model == 256:
-                return _ops.linear(sampled, self.output_proj.weight, self.output_proj.bias, residual=post[0].contiguous(),
-                                   norm=post[1])
-            out = self.output_proj(sampled)
-            return apply_post(post, out)
-        if isinstance(query, tuple):
-            query = query[0] + query[1]
+        route = self._route(q_parts, reference_points, input_flatten, value, host)
+        if route in ("level", "fused"):
+            # value_proj (+ masked_fill of padded tokens), [offsets | logits] in one GEMM (+ the caller's ``src + pos`` add
+            # when handed over as a (src, pos) pair), fused sampling.  "level": the level lives in LDS and the three
+            # projections exchange block-major operands with the kernel (include/dfx_msda.h); a handed-over ``value`` is
+            # row-major and not used
+            level = route == "level"
+            w, b = self._qproj_params_by_head() if level else self._qproj_params()
+            if level or value is None:
+                value = self._project_values(input_flatten, input_padding_mask, True, col_block=4 if level else 0)
+            qproj = _ops.linear(q_parts[0].contiguous(), w, b, add=q_parts[1].contiguous() if len(q_parts) > 1 else None,
+                                col_block=12 if level else 0)
+            if level:
+                sampled = _ops.msda_level_forward(value, reference_points, qproj, N, host[0][0], host[0][1])
+            else:
+                sampled = _ops.msda_fused_forward(value.view(N, S, M, D), input_spatial_shapes, input_level_start_index,
+                                                  reference_points, qproj, L, P)
+            return self._project_output(sampled, post, N, Lq, fuse_post=True, blocked=level)
 
+        query = q_parts[0] + q_parts[1] if len(q_parts) > 1 else query
         if value is None:
-            value = self.value_proj(input_flatten)
-            if input_padding_mask is not None:
-                value = value.masked_fill(input_padding_mask[..., None], float(0))
+            value = self._project_values(input_flatten, input_padding_mask, False)
         value = value.view(N, S, M, D)
-
-        if (MSDA_TRAIN and value.is_cuda and not torch.is_autocast_enabled() and reference_points.shape[2] == L
-                and value.dtype == query.dtype == reference_points.dtype == torch.float32
-                and _ops.fused_supported(value, M, D, L, P, reference_points.shape[2])):
+        if route == "train":
             # grad mode on the fused front end: the four Linear layers stay the modules they are, what lies between
             # them is one launch forwards and one backwards (csrc/msda_fused.hip, csrc/msda_fused_backward.hip);
             # no sampling_locations / attention_weights tensors exist, the node saves the Linear outputs only
             sampled = _ops.msda_fused(value.contiguous(), input_spatial_shapes, input_level_start_index, reference_points,
                                       self.sampling_offsets(query), self.attention_weights(query), L, P)
-            return apply_post(post, self.output_proj(sampled))
+            return self._project_output(sampled, post, N, Lq)
 
         offsets = self.sampling_offsets(query).view(N, Lq, M, L, P, 2)
         weights = F.softmax(self.attention_weights(query).view(N, Lq, M, L * P), -1).view(N, Lq, M, L, P)
@@ -201,8 +218,7 @@ class MSDeformAttn(nn.Module):
         else:
             sampled = _func.MSDeformAttnFunction.apply(value, input_spatial_shapes, input_level_start_index,
                                                        locations, weights, self.im2col_step)
-        out = self.output_proj(sampled)
-        return apply_post(post, out)
+        return self._project_output(sampled, post, N, Lq)
 
 
 _STACK_VALUES = os.environ.get("DFX_VALUE_STACK", "1") == "1"          # 0: every layer projects its own values (A/B runs)

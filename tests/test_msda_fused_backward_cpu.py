@@ -87,3 +87,25 @@ def test_module_on_the_cpu_never_takes_the_fused_training_branch(cpu_msda, monke
     out = m(query, torch.rand(2, 5, 2, 2), torch.randn(2, S, 256), shapes, lsi)
     out.sum().backward()
     assert calls[0] == 1 and query.grad is not None
+
+
+@pytest.mark.parametrize("what,text", [("level_start_index length", "level_start_index"), ("fp64 value", "float32"),
+                                       ("int32 spatial_shapes", "int64"), ("3-d reference_points", "reference_points")])
+def test_joint_and_split_form_reject_the_same_operands(what, text):
+    """The operand contract is checked before placement, so CPU tensors reach it: each malformed operand is named by the
+    forward on the joint row, the trainable form and the backward alike (well-formed CPU operands: the test above)."""
+    from dfx import ops
+    case = fc.make_case(2, 2, 3, 37)
+    value, shapes, lsi, ref, offsets, logits = (case[k] for k in ("value", "shapes", "lsi", "ref", "offsets", "logits"))
+    value, shapes, lsi, ref = {
+        "level_start_index length": (value, shapes, torch.cat([lsi, lsi[-1:]]), ref),
+        "fp64 value": (value.double(), shapes, lsi, ref),
+        "int32 spatial_shapes": (value, shapes.int(), lsi, ref),
+        "3-d reference_points": (value, shapes, lsi, ref[:, :, 0]),
+    }[what]
+    with pytest.raises(RuntimeError, match=text):
+        ops.msda_fused(value, shapes, lsi, ref, offsets, logits, 2, 4)
+    with pytest.raises(RuntimeError, match=text):
+        ops.msda_fused_forward(value, shapes, lsi, ref, torch.cat([offsets, logits], -1), 2, 4)
+    with pytest.raises(RuntimeError, match=text):
+        ops.msda_fused_backward(case["grad_out"], value, shapes, lsi, ref, offsets, logits)

@@ -296,15 +296,13 @@ def _level_expect(oracle, value, qproj, ref, H, W):
 
 
 def _run_level(value, qproj, ref, H, W, level):
+    """The level-in-LDS kernel (level) or the wave-per-query kernel on the same operands in the reference layouts."""
     from dfx import ops
     from models.transformer_layers import make_level_tensors
+    if level:
+        return ops.msda_level_forward_reference(value.cuda(), ref.cuda(), qproj.cuda(), H, W)
     shapes, lsi = make_level_tensors([(H, W)], "cuda")
-    saved = ops.USE_LEVEL_KERNEL, ops.LEVEL_MIN_QUERIES, ops.LEVEL_ON_REFERENCE_LAYOUTS
-    try:
-        ops.USE_LEVEL_KERNEL, ops.LEVEL_MIN_QUERIES, ops.LEVEL_ON_REFERENCE_LAYOUTS = level, 0, True
-        return ops.msda_fused_forward(value.cuda(), shapes, lsi, ref.cuda(), qproj.cuda(), 1, 4)
-    finally:
-        ops.USE_LEVEL_KERNEL, ops.LEVEL_MIN_QUERIES, ops.LEVEL_ON_REFERENCE_LAYOUTS = saved
+    return ops.msda_fused_forward(value.cuda(), shapes, lsi, ref.cuda(), qproj.cuda(), 1, 4)
 
 
 def _run_level_blocked(value, qproj, ref, H, W):

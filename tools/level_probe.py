@@ -11,7 +11,6 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 import torch
 
 from dfx import ops
-ops.LEVEL_ON_REFERENCE_LAYOUTS = True      # these probes compare the kernels on the reference layouts too
 from models.transformer_layers import make_level_tensors
 
 
@@ -36,12 +35,10 @@ def main():
     qproj_blk = torch.cat([qproj[..., :64].view(N, S, 8, 8), qproj[..., 64:].view(N, S, 8, 4)], -1) \
         .permute(2, 0, 1, 3).reshape(8, N * S, 12).contiguous()
     outs = {}
-    for mode in ("wave", "level", "level_blk"):
-        ops.USE_LEVEL_KERNEL = mode == "level"
-        if mode == "level_blk":
-            run = lambda: ops.msda_level_forward(value_blk, ref, qproj_blk, N, H, W)
-        else:
-            run = lambda: ops.msda_fused_forward(value, shapes, lsi, ref, qproj, 1, P)
+    runs = {"wave": lambda: ops.msda_fused_forward(value, shapes, lsi, ref, qproj, 1, P),
+            "level": lambda: ops.msda_level_forward_reference(value, ref, qproj, H, W),
+            "level_blk": lambda: ops.msda_level_forward(value_blk, ref, qproj_blk, N, H, W)}
+    for mode, run in runs.items():
         if load:
             a = torch.randn(4096, 4096, device=dev)
             for _ in range(iters):
