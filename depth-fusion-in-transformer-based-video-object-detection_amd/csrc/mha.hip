@@ -1,5 +1,7 @@
 // Fused scaled-dot-product attention for the 300-query layers (include/dfx_mha.h) on the gfx950 matrix
 // cores, fp32 (v_mfma_f32_32x32x2_f32), online softmax, nothing but the output leaves the CU.
+// In grad mode (dfx_mha_train_forward_f32, the TRAIN instantiations) the log-sum-exp of every query leaves too, and a dropout mask
+// may come in; the backward is csrc/mha_backward.hip.
 //
 // Wave = 32 queries of one (batch element, head); workgroup = WAVES waves sharing the key / value tiles
 // of 32 rows that all of them need (LDS, 8.5 KB).  Everything is computed TRANSPOSED so that no matrix
@@ -24,21 +26,23 @@
 // meet in LDS at the end and group 0 merges them with the usual log-sum-exp rescaling (same result up to the order of the sums).
 #include "dfx_common.h"
 #include "dfx_mha.h"
+#include "mha_tile.h"
 #include <stdlib.h>
 
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-constexpr int D = 32;          // head dimension
-constexpr int TK = 32;         // keys per tile
-constexpr int KP = 36;         // K tile row pitch (floats): 9 sixteen-byte slots, conflict-free ds_read_b128
-constexpr int WAVES = 2;       // 64 queries per workgroup
+using namespace dfx_mha;
 
-template <int GROUPS>
+// TRAIN (dfx_mha_train_forward_f32): the same walk, and also  lse[b,h,i] = ln sum_j exp(scale <q_i, k_j>)  for the backward's
+// recomputation, and an optional mask `drop` [B,heads,Lq,Lk] that multiplies the numerators on their way into the second
+// product (the denominator stays the undropped sum).  Both are compile-time additions behind scalar branches: with
+// drop == nullptr the arithmetic on `out` is the inference kernel's, instruction for instruction.
+template <int GROUPS, bool TRAIN>
 __global__ __launch_bounds__(64 * WAVES * GROUPS) void mha_fwd(const float *__restrict__ q, long q_batch, long q_row,
                                                       const float *__restrict__ k, long k_batch, long k_row,
                                                       const float *__restrict__ v, long v_batch, long v_row,
-                                                      float *__restrict__ out, long o_batch, long o_row, int Lq,
+                                                      float *__restrict__ out, long o_batch, long o_row,
+                                                      float *__restrict__ lse, const float *__restrict__ drop, int Lq,
                                                       int Lk, float scale)
 {
     constexpr int GT = 64 * WAVES;                                     // threads of a wave group
@@ -70,6 +74,10 @@ __global__ __launch_bounds__(64 * WAVES * GROUPS) void mha_fwd(const float *__re
     for (int r = 0; r < 16; ++r) o[r] = 0.f;
     float m = -INFINITY, lsum = 0.f;                                   // lsum: this lane half's part of the denominator
     const float *kb = k + b * k_batch + hd * D, *vb = v + b * v_batch + hd * D;
+
+    // (TRAIN) this lane's mask row, at the first key of its lane half
+    const float *dr = TRAIN && drop ? drop + (((long)b * gridDim.y + hd) * Lq + min(qi, Lq - 1)) * Lk + 4 * half : nullptr;
+    const bool dvec = (Lk & 3) == 0;
 
     const int ntiles = (Lk + TK - 1) / TK, iters = (ntiles + GROUPS - 1) / GROUPS;
     for (int it = 0; it < iters; ++it) {
@@ -119,6 +127,13 @@ __global__ __launch_bounds__(64 * WAVES * GROUPS) void mha_fwd(const float *__re
             o[r] *= resc;
         }
         lsum = lsum * resc + psum;
+        if (TRAIN && dr) {                                             // (scalar) registers 4g..4g+3 = keys j0 + 8g + 4*half + 0..3
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const float4 d4 = drop4(dr + j0 + 8 * g, j0 + 8 * g + 4 * half, Lk, dvec);
+                s[4 * g] *= d4.x; s[4 * g + 1] *= d4.y; s[4 * g + 2] *= d4.z; s[4 * g + 3] *= d4.w;
+            }
+        }
         // ---- O^T += V^T P^T: MFMA r pairs key (r&3)+8(r>>2) (+4 for lane half 1) with p[r] ----
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -145,9 +160,16 @@ __global__ __launch_bounds__(64 * WAVES * GROUPS) void mha_fwd(const float *__re
             const float mg = p[16 * 64], lg = p[17 * 64];
             const float mn = fmaxf(m, mg);                             // m is finite: group 0 owns tile 0
             const float a = __builtin_amdgcn_exp2f(m - mn), bq = __builtin_amdgcn_exp2f(mg - mn);      // bq = 0 for a group that saw no key (m_g = -inf)
+            {
+                // every rounding spelled out (no contraction left to the compiler), so that the instantiations of this kernel
+                // cannot differ in it: the train forward has the inference entry's bits.  The forms are the ones the
+                // inference kernel has always computed (profiles/r11_mha_forward_isa.txt): o by fma on the rounded second product, l by fma in the inner
+                // steps and from two rounded products in the last one
+#pragma clang fp contract(off)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) o[r] = o[r] * a + p[r * 64] * bq;
-            l = l * a + lg * bq;
+                for (int r = 0; r < 16; ++r) o[r] = __builtin_fmaf(o[r], a, p[r * 64] * bq);
+                l = gq == GROUPS - 1 ? l * a + lg * bq : __builtin_fmaf(l, a, lg * bq);
+            }
             m = mn;
         }
     }
@@ -158,21 +180,22 @@ __global__ __launch_bounds__(64 * WAVES * GROUPS) void mha_fwd(const float *__re
         for (int g = 0; g < 4; ++g)                                    // registers 4g..4g+3 = channels 8g + 4*half + 0..3
             *reinterpret_cast<float4 *>(op + 8 * g + 4 * half) =
                 make_float4(o[4 * g] * inv, o[4 * g + 1] * inv, o[4 * g + 2] * inv, o[4 * g + 3] * inv);
+        // m is the maximum of the scores in the log2 domain, l the sum of 2^(score - m): ln sum e^score = (m + log2 l) ln 2
+        if (TRAIN && half == 0) lse[((long)b * gridDim.y + hd) * Lq + qi] = fmaf(m, LN2, __builtin_amdgcn_logf(l) * LN2);
     }
 }
 
-}  // namespace
-
-extern "C" int dfx_mha_f32(const float *q, long q_batch, long q_row, const float *k, long k_batch, long k_row,
-                           const float *v, long v_batch, long v_row, float *out, long o_batch, long o_row, int B,
-                           int heads, int Lq, int Lk, float scale, void *stream)
+template <bool TRAIN>
+int launch_fwd(const float *q, long q_batch, long q_row, const float *k, long k_batch, long k_row, const float *v, long v_batch,
+               long v_row, float *out, long o_batch, long o_row, float *lse, const float *drop, int B, int heads, int Lq, int Lk,
+               float scale, void *stream)
 {
     if (B < 0 || heads <= 0 || Lq < 0 || Lk < 0) return dfx::fail(DFX_EINVAL, "mha: bad dimension");
     if ((long)B * Lq == 0) return DFX_OK;
-    if (!q || !k || !v || !out) return dfx::fail(DFX_EINVAL, "mha: null pointer");
+    if (!q || !k || !v || !out || (TRAIN && !lse)) return dfx::fail(DFX_EINVAL, "mha: null pointer");
     if (Lk == 0) return dfx::fail(DFX_EINVAL, "mha: no keys (softmax over an empty set)");
     if (((q_batch | q_row | k_batch | k_row | v_batch | v_row | o_batch | o_row) & 3) || !dfx::aligned16(q) ||
-        !dfx::aligned16(k) || !dfx::aligned16(v) || !dfx::aligned16(out))
+        !dfx::aligned16(k) || !dfx::aligned16(v) || !dfx::aligned16(out) || !dfx::aligned16(drop))
         return dfx::fail(DFX_EINVAL, "mha: strides must be multiples of 4 floats, buffers 16-byte aligned");
     if (q_row < heads * D || k_row < heads * D || v_row < heads * D || o_row < heads * D)
         return dfx::fail(DFX_EINVAL, "mha: row strides smaller than heads * 32");
@@ -184,13 +207,32 @@ extern "C" int dfx_mha_f32(const float *q, long q_batch, long q_row, const float
     if (dfx::tuning().mha_groups) groups = dfx::tuning().mha_groups;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (groups == 4)
-        hipLaunchKernelGGL(mha_fwd<4>, grid, dim3(64 * WAVES * 4), 0, st, q, q_batch, q_row, k, k_batch, k_row, v, v_batch, v_row,
-                           out, o_batch, o_row, Lq, Lk, scale);
+        hipLaunchKernelGGL((mha_fwd<4, TRAIN>), grid, dim3(64 * WAVES * 4), 0, st, q, q_batch, q_row, k, k_batch, k_row, v, v_batch,
+                           v_row, out, o_batch, o_row, lse, drop, Lq, Lk, scale);
     else if (groups == 2)
-        hipLaunchKernelGGL(mha_fwd<2>, grid, dim3(64 * WAVES * 2), 0, st, q, q_batch, q_row, k, k_batch, k_row, v, v_batch, v_row,
-                           out, o_batch, o_row, Lq, Lk, scale);
+        hipLaunchKernelGGL((mha_fwd<2, TRAIN>), grid, dim3(64 * WAVES * 2), 0, st, q, q_batch, q_row, k, k_batch, k_row, v, v_batch,
+                           v_row, out, o_batch, o_row, lse, drop, Lq, Lk, scale);
     else
-        hipLaunchKernelGGL(mha_fwd<1>, grid, dim3(64 * WAVES), 0, st, q, q_batch, q_row, k, k_batch, k_row, v, v_batch, v_row,
-                           out, o_batch, o_row, Lq, Lk, scale);
+        hipLaunchKernelGGL((mha_fwd<1, TRAIN>), grid, dim3(64 * WAVES), 0, st, q, q_batch, q_row, k, k_batch, k_row, v, v_batch,
+                           v_row, out, o_batch, o_row, lse, drop, Lq, Lk, scale);
     return dfx::check_launch("mha_fwd");
+}
+
+}  // namespace
+
+extern "C" int dfx_mha_f32(const float *q, long q_batch, long q_row, const float *k, long k_batch, long k_row,
+                           const float *v, long v_batch, long v_row, float *out, long o_batch, long o_row, int B,
+                           int heads, int Lq, int Lk, float scale, void *stream)
+{
+    return launch_fwd<false>(q, q_batch, q_row, k, k_batch, k_row, v, v_batch, v_row, out, o_batch, o_row, nullptr, nullptr, B,
+                             heads, Lq, Lk, scale, stream);
+}
+
+extern "C" int dfx_mha_train_forward_f32(const float *q, long q_batch, long q_row, const float *k, long k_batch, long k_row,
+                                         const float *v, long v_batch, long v_row, float *out, long o_batch, long o_row,
+                                         float *lse, const float *drop, int B, int heads, int Lq, int Lk, float scale,
+                                         void *stream)
+{
+    return launch_fwd<true>(q, q_batch, q_row, k, k_batch, k_row, v, v_batch, v_row, out, o_batch, o_row, lse, drop, B, heads,
+                            Lq, Lk, scale, stream);
 }

@@ -781,9 +781,7 @@ def dynamic_conv(feats, params, norm1, norm2):
     return _dynamic_conv_forward(feats, params, norm1, norm2)
 
 
-def mha(q, k, v, heads, scale):
-    """softmax(scale * q k^T) v per head (include/dfx_mha.h): q [B,Lq,E], k / v [B,Lk,E], E = 32*heads, fp32.
-    The tensors may be column slices of a joint projection (last dimension contiguous).  -> [B,Lq,E]"""
+def _mha_checks(q, k, v, heads):
     for nm, t in (("q", q), ("k", k), ("v", v)):
         if not t.is_cuda:
             raise RuntimeError(f"{nm} must be a CUDA tensor (the fused attention has no CPU path)")
@@ -792,6 +790,87 @@ def mha(q, k, v, heads, scale):
     B, Lq, E = q.shape
     Lk = k.shape[1]
     _require(k.shape == (B, Lk, E) and v.shape == (B, Lk, E), "mha: k and v must be [B,Lk,E]")
+    return B, Lq, Lk, E
+
+
+def _mha_drop(drop, q, B, heads, Lq, Lk):
+    """data pointer of the dropout mask ([B,heads,Lq,Lk] or [B*heads,Lq,Lk], contiguous fp32), None without one"""
+    if drop is None:
+        return None
+    _require(drop.is_cuda and drop.device == q.device and drop.dtype == torch.float32 and drop.is_contiguous()
+             and tuple(drop.shape) in ((B, heads, Lq, Lk), (B * heads, Lq, Lk)),
+             "mha: drop must be a contiguous fp32 [B,heads,Lq,Lk] (or [B*heads,Lq,Lk]) tensor on q's device")
+    return drop.data_ptr()
+
+
+def _strided(t):
+    return (t.data_ptr(), t.stride(0), t.stride(1))
+
+
+def mha_train_forward(q, k, v, heads, scale, drop=None):
+    """The attention with what its backward needs (include/dfx_mha.h, dfx_mha_train_forward_f32): -> (out [B,Lq,E],
+    lse [B,heads,Lq] = ln sum_j exp(scale <q_i,k_j>)).  drop (0 or 1/(1-p)) multiplies the normalised probabilities.
+    No autograd node; without ``drop`` the output has the bits of the inference entry."""
+    B, Lq, Lk, E = _mha_checks(q, k, v, heads)
+    out = torch.empty((B, Lq, E), dtype=torch.float32, device=q.device)
+    lse = torch.empty((B, heads, Lq), dtype=torch.float32, device=q.device)
+    _call("mha", "dfx_mha_train_forward_f32", q.device, *_strided(q), *_strided(k), *_strided(v), out.data_ptr(), Lq * E, E,
+          lse.data_ptr(), _mha_drop(drop, q, B, heads, Lq, Lk), B, heads, Lq, Lk, float(scale))
+    return out, lse
+
+
+def mha_backward(grad_out, q, k, v, out, lse, heads, scale, drop=None, need_q=True, need_kv=True):
+    """Gradients of ``mha`` (include/dfx_mha.h, dfx_mha_backward_f32) from its inputs, its output and ``lse`` of
+    ``mha_train_forward``; the probabilities are recomputed.  -> (grad_q | None, grad_k | None, grad_v | None), each
+    contiguous; grad_k and grad_v come together.  One launch without atomics: two calls give the same bits."""
+    B, Lq, Lk, E = _mha_checks(q, k, v, heads)
+    for nm, t in (("grad_out", grad_out), ("out", out)):
+        _require(t.is_cuda and t.device == q.device and t.dtype == torch.float32 and tuple(t.shape) == (B, Lq, E)
+                 and t.stride(2) == 1, f"mha_backward: {nm} must be [B,Lq,E] fp32 with a contiguous last dimension")
+    _require(lse.is_cuda and lse.device == q.device and lse.dtype == torch.float32 and tuple(lse.shape) == (B, heads, Lq)
+             and lse.is_contiguous(), "mha_backward: lse must be a contiguous fp32 [B,heads,Lq] tensor")
+    grad_q = torch.empty((B, Lq, E), dtype=torch.float32, device=q.device) if need_q else None
+    grad_k = torch.empty((B, Lk, E), dtype=torch.float32, device=q.device) if need_kv else None
+    grad_v = torch.empty((B, Lk, E), dtype=torch.float32, device=q.device) if need_kv else None
+    if need_q or need_kv:
+        _call("mha_backward", "dfx_mha_backward_f32", q.device, *_strided(grad_out), *_strided(q), *_strided(k), *_strided(v),
+              *_strided(out), lse.data_ptr(), _mha_drop(drop, q, B, heads, Lq, Lk), _ptr(grad_q), Lq * E, E, _ptr(grad_k),
+              Lk * E, E, _ptr(grad_v), Lk * E, E, B, heads, Lq, Lk, float(scale))
+    return grad_q, grad_k, grad_v
+
+
+class _MhaFunction(torch.autograd.Function):
+    """apply(q, k, v, drop, heads, scale): saves q, k, v, out, lse and the mask; nothing of size Lq x Lk but the mask."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, drop, heads, scale):
+        out, lse = mha_train_forward(q, k, v, heads, scale, drop)
+        ctx.heads, ctx.scale = heads, scale
+        ctx.save_for_backward(q, k, v, out, lse, drop)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        q, k, v, out, lse, drop = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        gq, gk, gv = mha_backward(grad_output.contiguous(), q, k, v, out, lse, ctx.heads, ctx.scale, drop, need_q=need[0],
+                                  need_kv=need[1] or need[2])
+        return gq, gk if need[1] else None, gv if need[2] else None, None, None, None
+
+
+def mha(q, k, v, heads, scale, drop=None):
+    """softmax(scale * q k^T) v per head (include/dfx_mha.h): q [B,Lq,E], k / v [B,Lk,E], E = 32*heads, fp32.
+    The tensors may be column slices of a joint projection (last dimension contiguous).  -> [B,Lq,E]
+    drop [B,heads,Lq,Lk] (0 or 1/(1-p)): attention dropout, multiplies the normalised probabilities.
+    With grad mode on and q, k or v requiring a gradient the result carries it back through ``mha_backward``; otherwise
+    no autograd node is made and, without a mask, the call is the inference entry dfx_mha_f32."""
+    if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
+        _mha_checks(q, k, v, heads)
+        return _MhaFunction.apply(q, k, v, drop, heads, float(scale))
+    if drop is not None:
+        return mha_train_forward(q, k, v, heads, scale, drop)[0]
+    B, Lq, Lk, E = _mha_checks(q, k, v, heads)
     out = torch.empty((B, Lq, E), dtype=torch.float32, device=q.device)
     _call("mha", "dfx_mha_f32", q.device, q.data_ptr(), q.stride(0), q.stride(1), k.data_ptr(), k.stride(0), k.stride(1),
           v.data_ptr(), v.stride(0), v.stride(1), out.data_ptr(), Lq * E, E, B, heads, Lq, Lk, float(scale))

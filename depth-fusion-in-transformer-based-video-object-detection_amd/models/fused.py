@@ -53,3 +53,13 @@ def apply_post(post, out):
     if drop is not None:
         out = drop(out)
     return post[1](post[0] + out)
+
+
+def has_hooks(module):
+    """True when calling ``module`` would run a forward, forward-pre or backward hook: one registered on the module or a
+    global one (torch.nn.modules.module.register_module_*_hook), which runs for every module."""
+    from torch.nn.modules import module as _m
+    own = (module._forward_hooks, module._forward_pre_hooks, module._backward_hooks, getattr(module, "_backward_pre_hooks", None))
+    shared = (getattr(_m, name, None) for name in ("_global_forward_hooks", "_global_forward_pre_hooks", "_global_backward_hooks",
+                                                   "_global_backward_pre_hooks"))
+    return any(bool(h) for h in own) or any(bool(h) for h in shared)

@@ -13,23 +13,13 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from models.fused import Linear
+from models.fused import Linear, has_hooks
 from models.transformer_layers import _linear_norm_add, _norm_add
 
 _DEFAULT_SCALE_CLAMP = math.log(100000.0 / 16)
 # DynamicConv in grad mode on the fused forward + fused backward (csrc/dynconv_backward.hip); DFX_DYNCONV_TRAIN=0 keeps the
 # library route (bmm + LayerNorm + ReLU under autograd) for A/B runs.  Read once at import.
 DYNCONV_TRAIN = os.environ.get("DFX_DYNCONV_TRAIN", "1") != "0"
-
-
-def _has_hooks(module):
-    """True when calling ``module`` would run a forward, forward-pre or backward hook: one registered on the module or a
-    global one (torch.nn.modules.module.register_module_*_hook), which runs for every module."""
-    from torch.nn.modules import module as _m
-    own = (module._forward_hooks, module._forward_pre_hooks, module._backward_hooks, getattr(module, "_backward_pre_hooks", None))
-    shared = (getattr(_m, name, None) for name in ("_global_forward_hooks", "_global_forward_pre_hooks", "_global_backward_hooks",
-                                                   "_global_backward_pre_hooks"))
-    return any(bool(h) for h in own) or any(bool(h) for h in shared)
 
 
 def _get_activation_fn(activation):
@@ -62,7 +52,7 @@ class DynamicConv(nn.Module):
             return False
         if not torch.is_grad_enabled():
             return True
-        return DYNCONV_TRAIN and not (_has_hooks(self.norm1) or _has_hooks(self.norm2) or _has_hooks(self.activation))
+        return DYNCONV_TRAIN and not (has_hooks(self.norm1) or has_hooks(self.norm2) or has_hooks(self.activation))
 
     def forward(self, pro_features, roi_features, params=None):
         """pro_features (1, K, C); roi_features (49, K, C) -> (K, C).  ``params``: the output of ``dynamic_layer(pro_features)``

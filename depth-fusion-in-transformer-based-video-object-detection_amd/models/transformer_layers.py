@@ -52,7 +52,8 @@ def _linear_act(linear, activation, x):
 
 def _mha(module, q, k, v, post=None):
     """nn.MultiheadAttention on batch-first [B,L,E] tensors (no masks, attention weights unused): the fused
-    GEMM + attention-kernel route in GPU inference (models/fused_mha.py), the module itself otherwise.
+    GEMM + attention-kernel route on the GPU (models/fused_mha.py; in grad mode the attention kernel with its fused backward
+    between library Linears), the module itself otherwise.
     post = (residual, norm, dropout): -> norm(residual + dropout(attention output)) (one add_layernorm launch behind out_proj's GEMM
     on the fused route when the dropout is the identity)."""
     from . import fused_mha
@@ -473,7 +474,7 @@ class TemporalQueryEncoderLayer(nn.Module):
         """[rows, E] reference queries -> [rows, 2E] their key / value projections for ``forward(ref_kv=...)``, or None when
         the fused GPU route does not apply (the caller then hands the gathered queries over as before)."""
         from . import fused_mha
-        if fused_mha.usable(self.cross_attn, pool):
+        if not torch.is_grad_enabled() and fused_mha.usable(self.cross_attn, pool):
             return fused_mha.project_kv(self.cross_attn, pool)
         return None
 
