@@ -26,6 +26,8 @@ SIGNATURES = {
     # value, shapes, lsi, ref, ref_dim, off, off_stride, logits, logit_stride, grad_out, dims, grad_value | NULL,
     # grad_off, stride, grad_logits, stride, grad_ref | NULL, stream (csrc/msda_fused_backward.hip)
     "dfx_msda_fused_backward_f32": [_p, _p, _p, _p, _i, _p, _l, _p, _l, _p] + _DIMS + [_p, _p, _l, _p, _l, _p, _p],
+    # ref, ref_dim, off, off_pitch, logits, logit_pitch, grad_out, N, H, W, Lq, grad_value, stream (csrc/msda_level_backward.hip)
+    "dfx_msda_level_grad_value_f32": [_p, _i, _p, _l, _p, _l, _p, _i, _i, _i, _i, _p, _p],
     "dfx_profile_enable": [_i],
     "dfx_tuning_reload": [],
     "dfx_profile_drain": [_p, _p, _p, _p, _i],

@@ -22,6 +22,13 @@ ACT = {None: 0, "none": 0, "relu": 1, "gelu": 2}
 # kernel (A/B measurements).  LEVEL_MIN_QUERIES: below it staging the level costs more than it saves.
 USE_LEVEL_KERNEL = os.environ.get("DFX_MSDA_LEVEL", "1") == "1"
 LEVEL_MIN_QUERIES = 1024
+# In grad mode a single-level layer's grad_value is summed in LDS (csrc/msda_level_backward.hip) instead of by global
+# atomics when the level fits and the launch has enough queries; DFX_MSDA_LEVEL_BWD=0 keeps the atomics everywhere (A/B
+# measurements).  LEVEL_BWD_MIN_QUERIES (N * Lq) is the smallest launch MEASURED faster than the atomics beyond the
+# repetition spread (profiles/r12_msda_level_backward.txt, 50 x 84 level): 1.18x at 32 frames x 300 queries, 1.09x / 1.57x
+# at 4 / 32 frames x 4200; at 4 x 300 = 1200 the two routes tie inside a 20-35 % spread, and nothing between was measured.
+USE_LEVEL_BWD = os.environ.get("DFX_MSDA_LEVEL_BWD", "1") != "0"
+LEVEL_BWD_MIN_QUERIES = 9600
 # convolutions of <= 4 input channels from an LDS-resident input tile (csrc/conv_tile.hip); 0: on the implicit GEMM (A/B runs)
 USE_TILE_CONV = os.environ.get("DFX_TILE_CONV", "1") == "1"
 
@@ -283,8 +290,10 @@ def msda_fused_backward(grad_out, value, spatial_shapes, level_start_index, refe
     recomputes the softmax weights and the locations).  grad_out [N,Lq,M*D]; reference_points contiguous; offsets /
     logits as for msda_fused (rows may be column slices of a wider buffer).
     -> (grad_value [N,S,M,D] | None, grad_offsets like offsets, grad_logits like logits, grad_ref like reference_points | None)
-    grad_value is summed with float atomics and is only computed (and its buffer only allocated) with need_value; the
-    other three are plain stores: two calls on the same inputs give the same bits."""
+    grad_value is summed with float atomics - global ones into a zero-filled buffer, or, for a single level that
+    level_backward_supported admits, LDS ones in a second launch (dfx_msda_level_grad_value_f32) - and is only computed
+    (and its buffer only allocated) with need_value; the other three are plain stores: two calls on the same inputs give
+    the same bits."""
     N, S, M, D, L, Lq, P, _, ref_dim = _msda_fused_operands(
         "msda_fused_backward", value, spatial_shapes, level_start_index, reference_points,
         (("offsets", offsets, 2), ("logits", logits, 1)))
@@ -294,16 +303,82 @@ def msda_fused_backward(grad_out, value, spatial_shapes, level_start_index, refe
     offsets, off_pitch = _pitched_rows(offsets, N, Lq, M * L * P * 2)
     logits, logit_pitch = _pitched_rows(logits, N, Lq, M * L * P)
     dev = value.device
-    grad_value = torch.zeros_like(value) if need_value else None            # the one buffer the kernel accumulates into
+    # a single level that fits a CU's LDS under enough queries: the atomic-free instantiation for the small gradients, then
+    # grad_value summed in LDS by msda_level_grad_value (two launches, no global atomic, no zero fill)
+    hw = _level_backward_size(spatial_shapes, M, D, L, P, N, Lq) if need_value else None
+    if hw is not None:
+        # the kernel writes N * H * W rows and nothing else: a host copy of the sizes that disagrees with the value map
+        # (a shapes tensor changed in place) must not reach it
+        _require(hw[0] * hw[1] == S, "msda_fused_backward: the level's H * W differs from the value map's token count")
+        grad_value = torch.empty_like(value)
+    else:
+        grad_value = torch.zeros_like(value) if need_value else None        # the one buffer the kernel accumulates into
     grad_off = torch.empty((N, Lq, M * L * P * 2), dtype=torch.float32, device=dev)
     grad_logits = torch.empty((N, Lq, M * L * P), dtype=torch.float32, device=dev)
     grad_ref = torch.empty((N, Lq, L, ref_dim), dtype=torch.float32, device=dev) if need_ref else None
     _call("msda_fused_backward", "dfx_msda_fused_backward_f32", dev,
           value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(), reference_points.data_ptr(), ref_dim,
           offsets.data_ptr(), off_pitch, logits.data_ptr(), logit_pitch, grad_out.data_ptr(),
-          N, S, M, D, L, Lq, P, _ptr(grad_value), grad_off.data_ptr(), M * L * P * 2, grad_logits.data_ptr(), M * L * P,
-          _ptr(grad_ref))
+          N, S, M, D, L, Lq, P, None if hw is not None else _ptr(grad_value), grad_off.data_ptr(), M * L * P * 2,
+          grad_logits.data_ptr(), M * L * P, _ptr(grad_ref))
+    if hw is not None:
+        _call("msda_fused_backward", "dfx_msda_level_grad_value_f32", dev,
+              reference_points.data_ptr(), ref_dim, offsets.data_ptr(), off_pitch, logits.data_ptr(), logit_pitch,
+              grad_out.data_ptr(), N, hw[0], hw[1], Lq, grad_value.data_ptr())
     return grad_value, grad_off, grad_logits, grad_ref
+
+
+def level_backward_supported(L, H, W, N, Lq, M=8, D=32, P=4):
+    """Host decision: grad_value of this launch is summed in LDS by msda_level_grad_value (csrc/msda_level_backward.hip) -
+    one level, the fused geometry, a level that fits the CU's LDS, the switch on and enough queries in the launch."""
+    return (USE_LEVEL_BWD and L == 1 and M == 8 and D == 32 and P == 4 and N * Lq >= LEVEL_BWD_MIN_QUERIES
+            and H > 0 and W > 0 and bool(_lib.load().dfx_msda_fused_level_fits(int(H), int(W))))
+
+
+def _level_backward_size(spatial_shapes, M, D, L, P, N, Lq):
+    """(H, W) of the single level when level_backward_supported, else None.  The host sizes ride on the shapes tensor
+    (models.transformer_layers.make_level_tensors); a shapes tensor without them is read back once and keeps them."""
+    if L != 1 or N * Lq == 0 or not level_backward_supported(L, 1, 1, N, Lq, M, D, P):     # all but the level's size
+        return None
+    host = getattr(spatial_shapes, "_dfx_host", None)
+    if host is None:
+        host = [(int(h), int(w)) for h, w in spatial_shapes.tolist()]
+        spatial_shapes._dfx_host = host
+    H, W = host[0]
+    return (H, W) if level_backward_supported(L, H, W, N, Lq, M, D, P) else None
+
+
+def msda_level_grad_value(grad_out, reference_points, offsets, logits, N, H, W):
+    """grad_value of single-level fused MSDA summed in LDS (include/dfx_msda.h, dfx_msda_level_grad_value_f32), on the
+    operands of msda_fused_backward with one level.  A level that does not fit the CU's LDS raises; no other kernel steps in.
+
+    grad_out [N,Lq,256], reference_points [N,Lq,1,2|4], offsets [N,Lq,64], logits [N,Lq,32] (rows may be column slices of
+    a wider buffer), all fp32 on one GPU  -> [N,H*W,8,32], every element written; last bits may differ between calls."""
+    what = "msda_level_grad_value"
+    reference_points = _level_reference_points(reference_points, N)
+    Lq, ref_dim = reference_points.shape[1], reference_points.shape[3]
+    _require(ref_dim in (2, 4), f"{what}: reference_points must be [N, Lq, 1, 2|4]")
+    rows = (("grad_out", grad_out, 256), ("offsets", offsets, 64), ("logits", logits, 32))
+    # shapes and dtypes first, then placement (as _msda_fused_operands)
+    for name, t, width in rows:
+        if t.dim() != 3 or t.shape != (N, Lq, width):
+            raise RuntimeError(f"{what}: {name} must be [N,Lq,{width}]")
+        if t.dtype != torch.float32:
+            raise RuntimeError(f"{what} is implemented for float32")
+    _check_inputs([("reference_points", reference_points)])
+    for name, t, _ in rows:
+        if not t.is_cuda or t.device != reference_points.device:
+            raise RuntimeError(f"Not implemented on the CPU ({name} must be a CUDA tensor on {reference_points.device})")
+    _require(H > 0 and W > 0 and bool(_lib.load().dfx_msda_fused_level_fits(int(H), int(W))),
+             f"{what}: a {H} x {W} level does not fit the level-in-LDS kernel")
+    grad_out = grad_out.contiguous()
+    offsets, off_pitch = _pitched_rows(offsets, N, Lq, 64)
+    logits, logit_pitch = _pitched_rows(logits, N, Lq, 32)
+    grad_value = torch.empty((N, H * W, 8, 32), dtype=torch.float32, device=grad_out.device)
+    _call(what, "dfx_msda_level_grad_value_f32", grad_out.device,
+          reference_points.data_ptr(), ref_dim, offsets.data_ptr(), off_pitch, logits.data_ptr(), logit_pitch,
+          grad_out.data_ptr(), N, int(H), int(W), Lq, grad_value.data_ptr())
+    return grad_value
 
 
 class _MSDAFusedFunction(torch.autograd.Function):

@@ -220,6 +220,34 @@ int dfx_msda_fused_level_forward_f32(const float *value, const float *ref, int r
                                      const dfx_msda_level_layout *layout,
                                      int N, int H, int W, int Lq, float *out, void *stream);
 
+/*
+ * grad_value of the single-level fused operator, summed in LDS (training; csrc/msda_level_backward.hip): the value
+ * gradient of dfx_msda_fused_backward_f32 for L = 1, M = 8, D = 32, P = 4, fp32 and a level that fits
+ * (dfx_msda_fused_level_fits(H, W) != 0), without a global atomic.  One workgroup owns a (frame, head, channel octet)
+ * slice of grad_value, sums the contributions of ALL queries of the frame into an LDS image of the level and stores
+ * the finished slice once.  Together with dfx_msda_fused_backward_f32 called with grad_value == NULL (the three small
+ * gradients, no atomics) it is the whole backward of a single-level layer.  Replaces the grad_value part of
+ * ms_deform_attn_cuda_backward (ms_deform_attn_cuda.cu:83-153; the atomicAdd of ms_deform_im2col_cuda.cuh:301-920).
+ * Reference layouts only, pointers plus row pitches in floats as dfx_msda_fused_backward_f32 takes them:
+ *   ref        [N,Lq,1,ref_dim], ref_dim 2 or 4, 16-byte aligned (8 for ref_dim 2)
+ *   off        [N,Lq,64] raw sampling_offsets rows, `off_pitch` floats apart (>= 64, a multiple of 4)   \  16-byte aligned;
+ *   logits     [N,Lq,32] raw attention_weights rows, `logit_pitch` floats apart (>= 32, a multiple of 4) / may be column
+ *              slices of one wider buffer
+ *   grad_out   [N,Lq,256] contiguous
+ *   grad_value [N,H*W,8,32] contiguous, WRITTEN in full with plain 16-byte stores (every element has one writer, zeros
+ *              included): the caller need not initialise it.
+ * All argument checks run before any launch.  N == 0 returns DFX_OK without a launch; Lq == 0 with N > 0 writes zeros
+ * to grad_value.  N*Lq < 2^28.  The softmax and the sampling locations are the level forward's arithmetic.
+ * NOT bit-reproducible: the order of the LDS float adds is not fixed, so two calls may differ in the last bits - as
+ * the global-atomic grad_value of dfx_msda_fused_backward_f32.  An addition to the ABI: dfx_abi_version() stays.
+ */
+int dfx_msda_level_grad_value_f32(const float *ref, int ref_dim,
+                                  const float *off, long off_pitch,
+                                  const float *logits, long logit_pitch,
+                                  const float *grad_out,
+                                  int N, int H, int W, int Lq,
+                                  float *grad_value, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
