@@ -17,7 +17,7 @@
 //   first product: K / 2 MFMAs into ONE 16-register accumulator (a dependent 32x32x2 chain issues at the full rate),
 //      k ascending exactly as gemm_f32_kernel walks it, then + bias, + residual, ReLU in that order: Y is bit-equal to
 //      dfx_gemm_f32 / dfx_conv1x1_pair_f32 on the same operands.
-//   second product: the accumulator layout (lane = column, register r = row (r & 3) + 8 (r >> 2) + 4h) IS the B-operand
+//   second product: the accumulator layout (lane = column, register r = row acc_row(r, h)) IS the B-operand
 //      layout of k = 8j + 4h + t with r = 4j + t, so register r of the finished Y tile feeds MFMA r of the tile against
 //      the natural-order W1 fragment: 16 MFMAs per 32 output channels of Z, no lane movement, no LDS round trip.  A wave
 //      sums Z over all Co in ascending k pairs - the order of the standalone GEMM - so Z is bit-equal to it as well.
@@ -26,11 +26,11 @@
 // range checks: exact zeros on both operands of the surplus MFMAs.
 #include "dfx_common.h"
 #include "dfx_gemm.h"
+#include "mfma_tile.h"
 
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
+using namespace dfx::mfma;
 
 struct ChainArgs {
     const float *W3, *X1, *X2, *b3, *R, *W1, *b1;
@@ -52,7 +52,6 @@ __global__ __launch_bounds__(256, chain_blocks(KT, C1T)) void conv1x1_chain_kern
     constexpr int SLAB = W3_SZ + W1_SZ;
     constexpr int KQ = KT * 8;                                // float4 per W3 slab row
     constexpr int L3 = KT, L1 = C1T;                          // float4 per thread and slab: 32 KQ / 256, 32 C1T 8 / 256
-    constexpr unsigned kOut = 0x80000000u;
     __shared__ __attribute__((aligned(16))) float smem[SLAB];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -64,19 +63,16 @@ __global__ __launch_bounds__(256, chain_blocks(KT, C1T)) void conv1x1_chain_kern
     const unsigned HW = (unsigned)g.HW, K = (unsigned)g.K, Co = (unsigned)g.Co;
     const int K2 = g.K - g.K1;
 
-    auto rsrc = [](const float *p, long bytes) {
-        return __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p), 0, (int)bytes, 0x00020000);
-    };
     // a missing operand gets an empty extent: its loads return zeros (x + 0 is exact)
-    const __amdgpu_buffer_rsrc_t rsX1 = rsrc(g.X1 + bz * g.strideX1, (long)g.K1 * g.HW * 4);
-    const __amdgpu_buffer_rsrc_t rsX2 = rsrc(g.X2 ? g.X2 + bz * g.strideX2 : g.X1, g.X2 ? (long)K2 * g.HW * 4 : 0);
-    const __amdgpu_buffer_rsrc_t rsW3 = rsrc(g.W3, (long)g.Co * g.K * 4);
-    const __amdgpu_buffer_rsrc_t rsW1 = rsrc(g.W1, (long)g.C1 * g.Co * 4);
-    const __amdgpu_buffer_rsrc_t rsB3 = rsrc(g.b3 ? g.b3 : g.W3, g.b3 ? (long)g.Co * 4 : 0);
-    const __amdgpu_buffer_rsrc_t rsB1 = rsrc(g.b1 ? g.b1 : g.W1, g.b1 ? (long)g.C1 * 4 : 0);
-    const __amdgpu_buffer_rsrc_t rsR = rsrc(g.R ? g.R + bz * g.strideR : g.W3, g.R ? (long)g.Co * g.HW * 4 : 0);
-    const __amdgpu_buffer_rsrc_t rsY = rsrc(g.Y + bz * g.strideY, (long)g.Co * g.HW * 4);
-    const __amdgpu_buffer_rsrc_t rsZ = rsrc(g.Z + bz * g.strideZ, (long)g.C1 * g.HW * 4);
+    const __amdgpu_buffer_rsrc_t rsX1 = buffer(g.X1 + bz * g.strideX1, (long)g.K1 * g.HW * 4);
+    const __amdgpu_buffer_rsrc_t rsX2 = buffer(g.X2 ? g.X2 + bz * g.strideX2 : g.X1, g.X2 ? (long)K2 * g.HW * 4 : 0);
+    const __amdgpu_buffer_rsrc_t rsW3 = buffer(g.W3, (long)g.Co * g.K * 4);
+    const __amdgpu_buffer_rsrc_t rsW1 = buffer(g.W1, (long)g.C1 * g.Co * 4);
+    const __amdgpu_buffer_rsrc_t rsB3 = buffer(g.b3 ? g.b3 : g.W3, g.b3 ? (long)g.Co * 4 : 0);
+    const __amdgpu_buffer_rsrc_t rsB1 = buffer(g.b1 ? g.b1 : g.W1, g.b1 ? (long)g.C1 * 4 : 0);
+    const __amdgpu_buffer_rsrc_t rsR = buffer(g.R ? g.R + bz * g.strideR : g.W3, g.R ? (long)g.Co * g.HW * 4 : 0);
+    const __amdgpu_buffer_rsrc_t rsY = buffer(g.Y + bz * g.strideY, (long)g.Co * g.HW * 4);
+    const __amdgpu_buffer_rsrc_t rsZ = buffer(g.Z + bz * g.strideZ, (long)g.C1 * g.HW * 4);
 
     // ---- the wave's activation panel: operand q = 4j + t of lane (c, h) is X[8j + 4h + t][n] ----
     float xr[KT * 16];
@@ -143,7 +139,7 @@ __global__ __launch_bounds__(256, chain_blocks(KT, C1T)) void conv1x1_chain_kern
         f32x4 bb[4];
 #pragma unroll
         for (int r = 0; r < 16; ++r)
-            rr[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsR, (row0 + (r & 3) + 8 * (r >> 2)) * HW * 4u + ncol4, 0, 0));
+            rr[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsR, (row0 + acc_row(r, 0)) * HW * 4u + ncol4, 0, 0));
 #pragma unroll
         for (int j = 0; j < 4; ++j)
             bb[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsB3, (row0 + 8 * j) * 4u, 0, 0));
@@ -166,7 +162,7 @@ __global__ __launch_bounds__(256, chain_blocks(KT, C1T)) void conv1x1_chain_kern
             v += rr[r];
             v = __builtin_fmaxf(v, 0.f);
             acc[r] = v;
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rsY, (row0 + (r & 3) + 8 * (r >> 2)) * HW * 4u + ncol4, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rsY, (row0 + acc_row(r, 0)) * HW * 4u + ncol4, 0, 0);
         }
         // the next tile's slab (L2) on its way under the second product, into the registers the residual has left
         __builtin_amdgcn_sched_barrier(0);
@@ -201,7 +197,7 @@ __global__ __launch_bounds__(256, chain_blocks(KT, C1T)) void conv1x1_chain_kern
         for (int r = 0; r < 16; ++r) {
             float v = zacc[ct][r] + bb[r >> 2][r & 3];
             if (g.relu_z) v = __builtin_fmaxf(v, 0.f);
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rsZ, (row0 + (r & 3) + 8 * (r >> 2)) * HW * 4u + ncol4, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rsZ, (row0 + acc_row(r, 0)) * HW * 4u + ncol4, 0, 0);
         }
     }
 }

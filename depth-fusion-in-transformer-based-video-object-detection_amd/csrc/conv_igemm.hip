@@ -11,35 +11,27 @@
 // the 16 k rows of a K-step; k is wave-uniform, so the tap table entry comes through the scalar cache and
 // the bounds test is two unsigned compares per element.  Out-of-map taps read element 0 and are zeroed
 // when they are written to LDS, so the loads stay unconditional and in flight across the MFMAs of the
-// current K-step.  Everything else is the structure of gemm_f32.hip: 4 waves x (MT x NT) tiles of
-// v_mfma_f32_32x32x2_f32, BK = 16 double-buffered, weights [m][k] read by ds_read_b128 along k (one read
-// = the operand of four MFMAs), the gathered operand [k][n] by ds_read_b32, epilogue bias + activation
-// straight from the accumulators into NCHW.
+// current K-step.  Everything else is mfma_tile.h: 4 waves x (MT x NT) tiles of v_mfma_f32_32x32x2_f32, BK = 16
+// double-buffered, the [m][k] x [k][n] K-step (weights read by ds_read_b128 along k, one read = the operand of
+// four MFMAs, the gathered operand by ds_read_b32) and the epilogues (per-row bias + activation into NCHW).
 // MFMA-bound: 2*Co*K*P flops per image against 157 TFLOP/s.
 #include "dfx_common.h"
 #include "dfx_conv.h"
+#include "mfma_tile.h"
 
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
+using namespace dfx::mfma;
 
 struct IgemmArgs {
-    const float *X, *Wp;
-    const int2 *ktab;          // per k: {tap index ky*KW+kx (or -1: padding column), byte offset ci*H*W*4 + (ky*dil*W + kx*dil)*4}
-    const float *bias;
-    float *Y;
-    int Ci, H, W, Co, Ho, Wo, Kpad, stride, pad, act, KH, KW, dil;
-    long strideX, strideY;
-    int wide;                  // Ho*Wo % 4 == 0 and y 16-byte aligned: float4 epilogue through LDS
+    const float *X = nullptr, *Wp = nullptr;
+    const int2 *ktab = nullptr;// per k: {tap index ky*KW+kx (or -1: padding column), byte offset ci*H*W*4 + (ky*dil*W + kx*dil)*4}
+    const float *bias = nullptr;
+    float *Y = nullptr;
+    int Ci = 0, H = 0, W = 0, Co = 0, Ho = 0, Wo = 0, Kpad = 0, stride = 1, pad = 0, act = 0, KH = 1, KW = 1, dil = 1;
+    long strideX = 0, strideY = 0;
+    int wide = 0;              // Ho*Wo % 4 == 0 and y 16-byte aligned: float4 epilogue through LDS
 };
-
-__device__ __forceinline__ float activate(float v, int act)
-{
-    if (act == DFX_ACT_RELU) return fmaxf(v, 0.f);
-    if (act == DFX_ACT_GELU) return 0.5f * v * (1.f + erff(v * 0.70710678118654752440f));
-    return v;
-}
 
 // UT ("uniform tap"): Ci % 16 == 0, so the 16 k of a K-step are 16 input channels of ONE tap: one table entry, one validity
 // test and one offset select per K-step instead of eight of each, the eight loads differ in their scalar offset only.  (The
@@ -49,20 +41,19 @@ template <int BM, int WM, int WN, bool UT>
 __global__ __launch_bounds__(256) void conv_igemm_kernel(const IgemmArgs g)
 {
     constexpr int BN = 128, BK = 16;
-    constexpr int TM = BM / WM, TN = BN / WN, MT = TM / 32, NT = TN / 32;
-    constexpr int LDK = BK + 4, LDB = BN + 4, LDC = BN + 4;
+    using T = Tile<BM, BN, WM, WN, 256>;
+    constexpr int LDK = BK + 4, LDB = T::LDB;
     constexpr int A_F4 = BM * BK / 4, A_LOADS = (A_F4 + 255) / 256;
     constexpr int B_ROWS = BK / 2;                     // k rows per thread per K-step
-    constexpr int A_SZ = BM * LDK, B_SZ = BK * LDB, C_SZ = 64 * LDC;
+    constexpr int A_SZ = BM * LDK, B_SZ = BK * LDB, C_SZ = T::PR * T::LDC;
     constexpr int S_SZ = 2 * (A_SZ + B_SZ) > C_SZ ? 2 * (A_SZ + B_SZ) : C_SZ;
-    static_assert(WM * WN == 4 && TM % 32 == 0 && TN % 32 == 0, "bad wave layout");
-    __shared__ __attribute__((aligned(16))) float smem[S_SZ];
-    float (*const As)[BM][LDK] = reinterpret_cast<float (*)[BM][LDK]>(smem);
-    float (*const Bs)[B_SZ] = reinterpret_cast<float (*)[B_SZ]>(smem + 2 * A_SZ);
+    __shared__ __attribute__((aligned(16))) float smem[S_SZ];        // the two operand stages; the epilogues' transpose buffer
+    float (*const As)[A_SZ] = reinterpret_cast<float (*)[A_SZ]>(smem);               // As[buf]: [m][k]
+    float (*const Bs)[B_SZ] = reinterpret_cast<float (*)[B_SZ]>(smem + 2 * A_SZ);    // Bs[buf]: [k][n]
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave / WN, wn = wave % WN;
-    const int half = lane >> 5, c = lane & 31;
+    // ---- tile coordinates ---------------------------------------------------------------------------------------------
+    const int tid = threadIdx.x;
+    const Lane l = lane_of<T>(tid);
     // Tile order (placement only): one-dimensional grid, workgroup ids XCD-remapped (each XCD walks one contiguous range,
     // dfx_common.h), the output-channel block fastest - the Co / BM workgroups that gather the SAME input pixels run back to
     // back on one XCD, so the gathered operand comes from HBM once and from that XCD's L2 afterwards (round 3 measured 3.3x the
@@ -72,8 +63,9 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const IgemmArgs g)
     const int lin = dfx::xcd_remap((int)blockIdx.x, (int)gridDim.x);
     const int by = lin % ny, rest = lin / ny;
     const int m0 = by * BM, n0 = (rest % nx) * BN;
-    const long bz = rest / nx;
+    const long bz = __builtin_amdgcn_readfirstlane(rest / nx);      // (scalar: kept in SGPRs, so are the descriptors built from it)
 
+    // ---- operand staging: weights by 16-byte buffer loads, the gathered operand element by element --------------------
     // this thread's output pixel, the top-left input pixel of its receptive field, and a bit per tap that lies
     // inside the map (KH*KW <= 64)
     const int pl = tid & (BN - 1);
@@ -92,13 +84,12 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const IgemmArgs g)
     }
     // Buffer loads.  The image descriptor starts `bias_el` elements BEFORE the image, so that the per-lane offset of the
     // receptive field's top-left corner (which lies up to pad rows / columns outside the map) is never negative; the
-    // tap's own offset is the scalar offset of the instruction.  A lane whose tap is outside the map gets an offset
-    // beyond the extent and the hardware returns 0 for it: no clamp, no select, one shift + compare per element.
-    constexpr unsigned kOut = 0x80000000u;
+    // tap's own offset is the scalar offset of the instruction.  A lane whose tap is outside the map gets kOut
+    // and the hardware returns 0 for it: no clamp, no select, one shift + compare per element.
     const int bias_el = g.pad * g.W + g.pad;
     const float *Xn = g.X + bz * g.strideX - bias_el;
-    const __amdgpu_buffer_rsrc_t rsX = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(Xn), 0, (int)(((long)g.Ci * HW + bias_el) * 4), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(g.Wp), 0, (int)((long)g.Co * g.Kpad * 4), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsX = buffer(Xn, ((long)g.Ci * HW + bias_el) * 4);
+    const __amdgpu_buffer_rsrc_t rsW = buffer(g.Wp, (long)g.Co * g.Kpad * 4);
     const unsigned vx = (unsigned)(iy0 * g.W + ix0 + bias_el) * 4u;
     unsigned va[A_LOADS];
 #pragma unroll
@@ -107,20 +98,14 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const IgemmArgs g)
         va[i] = (m < g.Co && f < A_F4) ? ((unsigned)m * (unsigned)g.Kpad + (unsigned)kq * 4u) * 4u : kOut;
     }
 
-    f32x16 acc[MT][NT];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    f32x16 acc[T::MT][T::NT] = {};
 
     f32x4 ra[A_LOADS];
     float rb[B_ROWS];
     auto load_tiles = [&](int k0) {
 #pragma unroll
         for (int i = 0; i < A_LOADS; ++i) {
-            ra[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsW, va[i], 0, 0));
+            ra[i] = load4(rsW, va[i]);
             va[i] += BK * 4u;
         }
         if (UT) {
@@ -129,13 +114,13 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const IgemmArgs g)
             const int cstep = 2 * HW * 4;                                // k advances by 2 per row of this thread: 2 channels
 #pragma unroll
             for (int i = 0; i < B_ROWS; ++i)
-                rb[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsX, vo, e.y + i * cstep, 0));
+                rb[i] = load1(rsX, vo, e.y + i * cstep);
         } else {
 #pragma unroll
             for (int i = 0; i < B_ROWS; ++i) {
                 const int2 e = g.ktab[k0 + kb + 2 * i];                  // scalar load: k is wave-uniform
                 const bool ok = e.x >= 0 && ((taps >> (e.x & 63)) & 1ull);
-                rb[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsX, ok ? vx : kOut, e.y, 0));
+                rb[i] = load1(rsX, ok ? vx : kOut, e.y);
             }
         }
     };
@@ -144,147 +129,37 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const IgemmArgs g)
         for (int i = 0; i < A_LOADS; ++i) {
             const int f = tid + i * 256, row = f / (BK / 4), kq = f % (BK / 4);
             if (f >= A_F4) continue;
-            *reinterpret_cast<f32x4 *>(&As[buf][row][kq * 4]) = ra[i];
+            *reinterpret_cast<f32x4 *>(&As[buf][row * LDK + kq * 4]) = ra[i];
         }
 #pragma unroll
         for (int i = 0; i < B_ROWS; ++i) Bs[buf][(kb + 2 * i) * LDB + pl] = rb[i];
     };
 
+    // ---- K loop -----------------------------------------------------------------------------------------------------------
     const int steps = g.Kpad / BK;
     load_tiles(0);
     store_tiles(0);
     __syncthreads();
     for (int t = 0; t < steps; ++t) {
         const int buf = t & 1;
-        if (t + 1 < steps) load_tiles((t + 1) * BK);
-        constexpr int KJ = BK / 8;
-        f32x4 af[KJ][MT];
-#pragma unroll
-        for (int j = 0; j < KJ; ++j)
-#pragma unroll
-            for (int i = 0; i < MT; ++i)
-                af[j][i] = *reinterpret_cast<const f32x4 *>(&As[buf][wm * TM + i * 32 + c][j * 8 + half * 4]);
-        float bs[2][NT];
-#pragma unroll
-        for (int jn = 0; jn < NT; ++jn) bs[0][jn] = Bs[buf][(half * 4) * LDB + wn * TN + jn * 32 + c];
-#pragma unroll
-        for (int q = 0; q < BK / 2; ++q) {
-            const int j = q >> 2, tt = q & 3, cur = q & 1, nxt = cur ^ 1;
-            if (q + 1 < BK / 2) {
-                const int kn = ((q + 1) >> 2) * 8 + half * 4 + ((q + 1) & 3);
-#pragma unroll
-                for (int jn = 0; jn < NT; ++jn) bs[nxt][jn] = Bs[buf][kn * LDB + wn * TN + jn * 32 + c];
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int i = 0; i < MT; ++i) {
-#pragma unroll
-                for (int jn = 0; jn < NT; ++jn)
-                    acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[j][i][tt], bs[cur][jn], acc[i][jn], 0, 0, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
+        if (t + 1 < steps) load_tiles((t + 1) * BK);       // in flight during the MFMAs
+        kstep_kn<T, BK>(As[buf], Bs[buf], l, acc);
         if (t + 1 < steps) store_tiles(buf ^ 1);
         __syncthreads();
     }
 
-    float *Y = g.Y + bz * g.strideY;
+    // ---- epilogue dispatch (mfma_tile.h): Y_n[Co][P], per-row bias -------------------------------------------------------
+    Epilogue e;
+    e.C = g.Y + bz * g.strideY, e.ldc = P;
+    e.bias = g.bias, e.bias_per_row = 1;
+    e.M = g.Co, e.N = P, e.act = g.act;
+    const f32x4 no_prefetch[1] = {};
     if (g.wide && g.act != DFX_ACT_GELU && (long)(g.Co + BM) * P * 4 < (1L << 31)) {
-        // The lean epilogue of gemm_f32.hip (see there: the epilogue's vector instructions are matrix time of the other
-        // resident workgroups): one 32-row tile per wave and pass, a thread keeps its column quad, rows are m0 + r0 + D(pass, it)
-        // with D known at compile time, stores and the row bias through buffer descriptors of the exact extents (rows beyond Co
-        // fall past the extent, columns beyond the map start from an offset beyond everything), ReLU = one v_max each.
-        float *Ct = smem;
-        constexpr int PR = 64, CQ = BN / 4, RS = 256 / CQ, NIT = PR / RS;
-        constexpr int TPP = PR / (32 * WM), TP1 = TPP >= 1 ? TPP : 1;
-        constexpr bool BAL = TPP >= 1 && PR == TPP * 32 * WM && MT % TP1 == 0;
-        static_assert(!BAL || (32 * TP1) % RS == 0, "thread rows must not straddle wave tiles");
-        const int c4 = tid % CQ, r0 = tid / CQ, n = n0 + c4 * 4, mb = m0 + r0;
-        const unsigned cbase = n < P ? ((unsigned)mb * (unsigned)P + (unsigned)n) * 4u : 0x80000000u;
-        const __amdgpu_buffer_rsrc_t rsY = __builtin_amdgcn_make_buffer_rsrc(Y, 0, (int)((long)g.Co * P * 4), 0x00020000);
-        const __amdgpu_buffer_rsrc_t rsBias = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(g.bias ? g.bias : Y), 0, g.Co * 4, 0x00020000);
-        const bool has_bias = g.bias != nullptr;
-        const int relu = g.act == DFX_ACT_RELU;
-#pragma unroll
-        for (int ps = 0; ps < BM / PR; ++ps) {
-            float br[NIT];
-#pragma unroll
-            for (int it = 0; it < NIT; ++it) {
-                const int D = BAL ? ((it * RS) / (32 * TP1)) * TM + ps * TP1 * 32 + (it * RS) % (32 * TP1) : ps * PR + it * RS;
-                br[it] = has_bias ? __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsBias, (unsigned)(mb + D) * 4u, 0, 0)) : 0.f;
-            }
-            if (ps > 0) __syncthreads();
-#pragma unroll
-            for (int i = 0; i < MT; ++i) {
-                if (BAL ? i / TP1 != ps : (wm * TM + i * 32) / PR != ps) continue;
-                const int rb = (BAL ? (wm * TPP + i % TP1) * 32 : wm * TM + i * 32 - ps * PR) + 4 * half;
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-#pragma unroll
-                    for (int j = 0; j < NT; ++j)
-                        Ct[(rb + (r & 3) + 8 * (r >> 2)) * LDC + wn * TN + j * 32 + c] = acc[i][j][r];
-            }
-            __syncthreads();
-#pragma unroll
-            for (int it = 0; it < NIT; ++it) {
-                const int D = BAL ? ((it * RS) / (32 * TP1)) * TM + ps * TP1 * 32 + (it * RS) % (32 * TP1) : ps * PR + it * RS;
-                if (m0 + D >= g.Co) continue;                  // (scalar: the whole thread row lies beyond the last output channel)
-                f32x4 v = *reinterpret_cast<const f32x4 *>(&Ct[(r0 + it * RS) * LDC + c4 * 4]);
-                v += br[it];
-                if (relu) {
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) asm("v_max_f32 %0, 0, %1" : "=v"(v[u]) : "v"(v[u]));
-                }
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((__vector_size__(4 * sizeof(unsigned)))) unsigned, v), rsY,
-                                                       cbase + (unsigned)D * (unsigned)P * 4u, 0, 0);
-            }
-        }
-        return;
+        if (g.bias) return epilogue_lean<T, 2, false, false, false>(smem, acc, l, m0, n0, e, no_prefetch, false);
+        return epilogue_lean<T, 0, false, false, false>(smem, acc, l, m0, n0, e, no_prefetch, false);
     }
-    if (g.wide) {
-        // as gemm_f32.hip: accumulators through LDS, 64 tile rows at a time, out as float4 - whole 512-byte row segments
-        float *Ct = smem;
-#pragma unroll
-        for (int ps = 0; ps < BM / 64; ++ps) {
-            if (ps > 0) __syncthreads();
-#pragma unroll
-            for (int i = 0; i < MT; ++i) {
-                if ((wm * TM + i * 32) / 64 != ps) continue;
-                const int rbase = wm * TM + i * 32 - ps * 64 + 4 * half;
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-#pragma unroll
-                    for (int j = 0; j < NT; ++j)
-                        Ct[(rbase + (r & 3) + 8 * (r >> 2)) * LDC + wn * TN + j * 32 + c] = acc[i][j][r];
-            }
-            __syncthreads();
-#pragma unroll
-            for (int f0 = 0; f0 < 64 * BN / 4; f0 += 256) {
-                const int f = f0 + tid, row = f / (BN / 4), c4 = f % (BN / 4);
-                const int m = m0 + ps * 64 + row, n = n0 + c4 * 4;
-                if (m >= g.Co || n >= P) continue;
-                float4 v = *reinterpret_cast<const float4 *>(&Ct[row * LDC + c4 * 4]);
-                const float bv = g.bias ? g.bias[m] : 0.f;
-                v.x = activate(v.x + bv, g.act); v.y = activate(v.y + bv, g.act);
-                v.z = activate(v.z + bv, g.act); v.w = activate(v.w + bv, g.act);
-                *reinterpret_cast<float4 *>(Y + (long)m * P + n) = v;
-            }
-        }
-        return;
-    }
-#pragma unroll
-    for (int i = 0; i < MT; ++i) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int m = m0 + wm * TM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-            const float bv = g.bias ? g.bias[min(m, g.Co - 1)] : 0.f;
-#pragma unroll
-            for (int j = 0; j < NT; ++j) {
-                const int n = n0 + wn * TN + j * 32 + c;
-                if (m < g.Co && n < P) Y[(long)m * P + n] = activate(acc[i][j][r] + bv, g.act);
-            }
-        }
-    }
+    if (g.wide) return epilogue_float4<T, false>(smem, acc, l, m0, n0, e, no_prefetch, false);
+    epilogue_scalar<T>(acc, l, m0, n0, e);
 }
 
 template <int BM, int WM, int WN>
@@ -321,8 +196,12 @@ extern "C" int dfx_conv2d_igemm_f32(const float *x, const float *wp, const int *
     if (N > 65535) return dfx::fail(DFX_ERANGE, "conv2d_igemm: batch too large");
     if (act < 0 || act > 2) return dfx::fail(DFX_EINVAL, "conv2d_igemm: unknown activation");
     const int wide = ((Ho * Wo) & 3) == 0 && dfx::aligned16(y);
-    IgemmArgs g{x, wp, reinterpret_cast<const int2 *>(ktab), bias, y, Ci, H, W, Co, Ho, Wo, Kpad, stride, pad, act, KH, KW,
-                dilation, x_image_stride > 0 ? x_image_stride : (long)Ci * H * W, (long)Co * Ho * Wo, wide};
+    IgemmArgs g;
+    g.X = x, g.Wp = wp, g.ktab = reinterpret_cast<const int2 *>(ktab), g.bias = bias, g.Y = y;
+    g.Ci = Ci, g.H = H, g.W = W, g.Co = Co, g.Ho = Ho, g.Wo = Wo, g.Kpad = Kpad;
+    g.KH = KH, g.KW = KW, g.stride = stride, g.pad = pad, g.dil = dilation, g.act = act;
+    g.strideX = x_image_stride > 0 ? x_image_stride : (long)Ci * H * W, g.strideY = (long)Co * Ho * Wo;
+    g.wide = wide;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (Co <= 64) return launch<64, 1, 4>(g, N, st);
     const long t128 = (long)((Co + 127) / 128) * ((Ho * Wo + 127) / 128) * N;

@@ -29,12 +29,12 @@
 // MFMA-bound: 2 * 32 MT * Kpad flops per output pixel against 157 TFLOP/s.
 #include "dfx_common.h"
 #include "dfx_conv.h"
+#include "mfma_tile.h"
 #include <type_traits>
 
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
+using namespace dfx::mfma;
 using i32x4 = __attribute__((ext_vector_type(4))) int;
 
 constexpr int kTH = 8, kTW = 32, kThreads = 512, kMaxStage = 9;      // tile: 8 rows x 32 pixels, one row per wave
@@ -50,13 +50,6 @@ struct TileArgs {
     int nstage;            // staged elements per thread = ceil(Ci * IH * IW / 512) <= kMaxStage
     unsigned xbytes;       // extent of the input buffer the descriptor covers
 };
-
-__device__ __forceinline__ float activate(float v, int act)
-{
-    if (act == DFX_ACT_RELU) return fmaxf(v, 0.f);
-    if (act == DFX_ACT_GELU) return 0.5f * v * (1.f + erff(v * 0.70710678118654752440f));
-    return v;
-}
 
 template <int MT, int NS>
 __global__ __launch_bounds__(kThreads, 4) void conv_tile_kernel(const TileArgs g)      // 2 workgroups per CU: <= 128 registers
@@ -105,7 +98,7 @@ __global__ __launch_bounds__(kThreads, 4) void conv_tile_kernel(const TileArgs g
         s_lds[u] = e < nel ? ci * g.IH * PW + r * PW + (s == 2 ? (x & 1) * PWH + (x >> 1) : x) : -1;
         s_rx[u] = (ci << 16) | (r << 8) | x;                  // (IH, IW <= 255: checked on the host)
     }
-    const __amdgpu_buffer_rsrc_t rsX = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(g.X), 0, (int)g.xbytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsX = buffer(g.X, g.xbytes);
     constexpr unsigned kOut = 0xFFFFFFFCu;
     float st[NS];
     // The tile walk is wave-uniform: (image, tile row, tile column) advance by the grid size with two carries - scalar
@@ -174,7 +167,7 @@ __global__ __launch_bounds__(kThreads, 4) void conv_tile_kernel(const TileArgs g
 #pragma unroll
         for (int i = 0; i < MT; ++i)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][r] = bl[i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half];
+            for (int r = 0; r < 16; ++r) acc[i][r] = bl[i * 32 + acc_row(r, half)];
         const float *im = img + buf * IMG + pixbase;
         // (two K-steps per iteration on two register sets - the next step's fragments read under the current MFMAs - measured
         // 1.3 % faster on the stem with 12 spilled registers: not kept; four waves per SIMD hide the LDS latency)
@@ -205,15 +198,15 @@ __global__ __launch_bounds__(kThreads, 4) void conv_tile_kernel(const TileArgs g
         // (channels beyond Co fall past the extent: dropped) - no vector instruction per store ----
         {
             const int oy = cur.ty * kTH + py, ox = cur.tx * kTW + px;
-            const __amdgpu_buffer_rsrc_t rsY = __builtin_amdgcn_make_buffer_rsrc(g.Y + (long)cur.n * g.strideY, 0, (int)((unsigned)g.Co * P4), 0x00020000);
-            const unsigned pix = (oy < g.Ho && ox < g.Wo) ? (unsigned)(oy * g.Wo + ox) * 4u + (unsigned)(4 * half) * P4 : 0x80000000u;
+            const __amdgpu_buffer_rsrc_t rsY = buffer(g.Y + (long)cur.n * g.strideY, (unsigned)g.Co * P4);
+            const unsigned pix = (oy < g.Ho && ox < g.Wo) ? (unsigned)(oy * g.Wo + ox) * 4u + (unsigned)(4 * half) * P4 : dfx::mfma::kOut;
             auto write = [&](auto act_tag) {
                 constexpr int ACT = decltype(act_tag)::value;
 #pragma unroll
                 for (int i = 0; i < MT; ++i)
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
-                        const int cr = i * 32 + (r & 3) + 8 * (r >> 2);        // + 4 * half: this lane's channel
+                        const int cr = i * 32 + acc_row(r, 0);        // + 4 * half: this lane's channel
                         float v = acc[i][r];
                         if (ACT == DFX_ACT_RELU) asm("v_max_f32 %0, 0, %1" : "=v"(v) : "v"(v));
                         if (ACT == DFX_ACT_GELU) v = activate(v, DFX_ACT_GELU);

@@ -27,6 +27,7 @@
 // MFMA-bound: 2*16*Co*Ci flops per tile against 157 TFLOP/s = 2.25x the direct form's rate at equal speed.
 #include "dfx_common.h"
 #include "dfx_conv.h"
+#include "mfma_tile.h"
 #include <stdlib.h>
 
 // Diagnostic build only (tools/wino_stamp.py compiles this file with -DDFX_WINO_STAMP into its own library): waves 0 and 4 of
@@ -47,8 +48,7 @@ extern "C" int dfx_wino_set_stamp_buffer(void *p)
 
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
+using namespace dfx::mfma;
 
 struct WinoArgs {
     const float *X, *U, *bias;
@@ -62,13 +62,6 @@ struct WinoArgs {
     int lb0;             // first logical block of this launch
     int no_phase;        // A/B switch: every wave loads before and transforms after its MFMAs (no phase shift between SIMD partners)
 };
-
-__device__ __forceinline__ float activate(float v, int act)
-{
-    if (act == DFX_ACT_RELU) return fmaxf(v, 0.f);
-    if (act == DFX_ACT_GELU) return 0.5f * v * (1.f + erff(v * 0.70710678118654752440f));
-    return v;
-}
 
 constexpr int kCoB = 64, kTB = 64, kCK = 8;       // the weight tensor's blocking: 64 output channels x 8 input channels
 constexpr int kUChunk = 16 * 2 * kCoB * 4;        // floats per U chunk of a 64-channel block (8192)
@@ -162,8 +155,8 @@ __global__ __launch_bounds__(512) void conv_wino_kernel(const WinoArgs g)
         }
     }
     const bool xloader = X_ITEMS == 512 || tid < X_ITEMS;
-    const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(g.X), 0, (int)g.xbytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t urs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(g.U), 0, (int)g.ubytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t xrs = buffer(g.X, g.xbytes);
+    const __amdgpu_buffer_rsrc_t urs = buffer(g.U, g.ubytes);
     const unsigned ubase = (unsigned)(co0 / kCoB) * g.nchunk * (kUChunk * 4u);
     // U: the chunk of the 64-channel block is [pos][kq][64 co][4]; this workgroup stages its CW channels of every row
     // (128 channels = two neighbouring 64-channel blocks of the weight tensor)
@@ -189,16 +182,10 @@ __global__ __launch_bounds__(512) void conv_wino_kernel(const WinoArgs g)
     // U chunk: memory -> LDS by LDS-DMA (`buffer_load_dwordx4 ... lds`, 1 KiB per wave-instruction, U_LD per wave): the
     // staged image is lane-linear, so no registers and no ds_write are spent on the weights (half of the chunk's bytes)
     auto dma_u = [&](int ch, int buf) {
-#if defined(__HIP_DEVICE_COMPILE__)
-        typedef __attribute__((address_space(3))) void *lds_ptr;
         const unsigned us = ubase + (unsigned)ch * (kUChunk * 4u);
         float *lu = Us + buf * UCH;
 #pragma unroll
-        for (int i = 0; i < U_LD; ++i)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(urs, (lds_ptr)(lu + (wave_u + 8 * i) * 256), 16, uoff[i], us, 0, 0);
-#else
-        (void)urs; (void)ubase; (void)wave_u; (void)ch; (void)buf;
-#endif
+        for (int i = 0; i < U_LD; ++i) lds_dma16(urs, lu + (wave_u + 8 * i) * 256, uoff[i], us);
     };
     auto load_x = [&](int ch) {
         const unsigned xs = (unsigned)ch * (unsigned)(kCK * HW) * 4u;             // scalar offset

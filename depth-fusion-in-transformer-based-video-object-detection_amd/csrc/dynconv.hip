@@ -14,11 +14,11 @@
 // is in LDS before the other is loaded).
 #include "dfx_common.h"
 #include "dfx_roi.h"
+#include "mfma_tile.h"
 
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using f32x4 = __attribute__((ext_vector_type(4))) float;     // staging registers (plain vectors: arrays of HIP's float4 struct were left in scratch memory)
+using namespace dfx::mfma;     // (f32x4 staging registers: arrays of HIP's float4 struct were left in scratch memory)
 constexpr int C = 256, DD = 64, RP = 64;       // channels, dynamic dim, padded rows
 constexpr int XP = C + 4;                      // X / Y2 row pitch (floats): 65 sixteen-byte slots
 constexpr int YP = DD + 4;                     // Y1 row pitch: 17 slots
@@ -123,7 +123,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             }
 #pragma unroll
             for (int r = 0; r < 16; ++r)
-                ys[(mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * half) * YP + nh * 32 + col] = acc[r];
+                ys[(mt * 32 + acc_row(r, half)) * YP + nh * 32 + col] = acc[r];
         }
         __syncthreads();
         // ---- LayerNorm(64) + ReLU on the rows of Y1: 16 lanes per row, one float4 each ----
@@ -172,7 +172,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             for (int t = 0; t < 4; ++t)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int row = mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+                    const int row = mt * 32 + acc_row(r, half);
                     if (row < R) xs[row * XP + nh * 128 + t * 32 + col] = acc[t][r];
                 }
         }

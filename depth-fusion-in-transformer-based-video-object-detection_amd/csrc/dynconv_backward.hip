@@ -25,11 +25,11 @@
 // fixed order into one row of the [grid, 640] workspace; dynconv_ln_reduce sums the rows in order.  No atomics.
 #include "dfx_common.h"
 #include "dfx_roi.h"
+#include "mfma_tile.h"
 
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
+using namespace dfx::mfma;
 constexpr int C = 256, DD = 64, RP = 64;
 constexpr int XP = C + 4, YP = DD + 4;
 constexpr int X_F4 = (49 * C / 4 + 255) / 256;

@@ -4,6 +4,7 @@
 // Structure (CDNA4, wave64):
 //   workgroup = 256 threads = 4 waves laid out WM x WN over a BM x BN output tile; a wave owns
 //   (BM/WM) x (BN/WN) = MT x NT MFMA tiles of 32 x 32, i.e. MT*NT*16 accumulator registers per lane
+//   (mfma_tile.h: the tile geometry, the K-step over one LDS stage and the epilogues, shared with conv_igemm.hip)
 //   K is walked in steps of BK = 16 through a double-buffered LDS stage:
 //     As[buf][m][k]  - A (and Linear weights, Bs[buf][n][k]) arrive K-contiguous as 16-byte loads and
 //                      are stored as they are, one ds_write_b128 each; row pitch BK+4 floats = five
@@ -12,58 +13,58 @@
 //     Bs[buf][k][n]  - activations of a 1x1 convolution are already [K][N]: 16-byte LDS stores
 //   the next K-step's global loads are issued into registers before the 8 x MT*NT MFMAs of the
 //   current step, and written to the other LDS buffer after them: one barrier per K-step
-//   fragments: the MFMA sums over k in any order as long as A and B agree, so the 8 MFMAs of a
-//   K-step are numbered q = 4j + t and lane l (row/col l&31, half h = l>>5) feeds MFMA q with
-//   k = 8j + 4h + t: one ds_read_b128 at [row][8j + 4h] yields the lane's operand of FOUR MFMAs
-//   (the [K][N] operand reads the same k with ds_read_b32, as its rows run along n)
-//   epilogue straight from the accumulators (row = (r&3) + 8*(r>>2) + 4*(l>>5), col = l&31):
-//   + bias (per row for convolutions, per column for Linear), + residual, ReLU, zeroing of masked
-//   rows; every store instruction writes 2 rows x 128 contiguous bytes.
+//   epilogue: + bias (per row for convolutions, per column for Linear), + residual, ReLU, zeroing of masked
+//   rows; through LDS and out as float4 where C allows it, else straight from the accumulators.
 // MFMA-bound: 2*M*N*K flops against 157 TFLOP/s (fp32 matrix peak, MI355X_MICROARCH.md).
 #include "dfx_common.h"
 #include "dfx_gemm.h"
+#include "mfma_tile.h"
 #include <stdlib.h>
-#include <type_traits>
 
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
+using namespace dfx::mfma;
 
 struct Args {
-    const float *A, *A2;
-    long lda, strideA;
-    const float *B;
-    long ldb, strideB;
-    const float *bias;
-    int bias_per_row;
-    const float *R;
-    long ldr, strideR;
-    const unsigned char *mask;
-    long strideMask;
-    float *C;
-    long ldc, strideC;
-    int M, N, K, relu;
-    int cblk;             // > 0: C is stored column-block-major, [ceil(N / cblk)][M][cblk] (include/dfx_gemm.h)
-    long cblk_stride;     // elements between column blocks (>= M * cblk)
-    long ablk_stride;     // > 0: A is K-block-major, [K / 4][M][4] with this many elements between blocks
-    int wide_epilogue;    // row-major C (and R) with 16-byte aligned rows, N % 4 == 0: float4 epilogue through LDS
-    int splits, kper;     // split-K: z = batch * splits + split, split s covers k in [s * kper, min(K, (s + 1) * kper))
-    int nx, ny;           // tiles along N and M (the grid is one-dimensional: nx * ny * nz workgroups)
-    const float *B2;      // two-segment [K,N] operand: rows k >= K1 come from B2 (row k - K1), same ldb; LDS-DMA path only
-    long strideB2;
-    int K1;
-    int group_m;          // tile order (placement only, never results): 0 = n fastest, then m, then z, as dispatched;
-                          // > 0: workgroup ids are XCD-remapped (each XCD walks one contiguous range) and run m fastest inside
-                          // groups of group_m tile rows, then along the columns of every batch element
-    int fast_cblk;        // column-block-major C through the same LDS round trip (set by launch())
-    int fast_epi;         // wide epilogue in its lean form (set by launch(): no GELU, C and R slices < 2 GiB)
-    long strideBias;      // elements the column bias advances per batch element (wide column blocks run as a batch: dfx_gemm_f32)
+    const float *A = nullptr, *A2 = nullptr;
+    long lda = 0, strideA = 0;
+    const float *B = nullptr;
+    long ldb = 0, strideB = 0;
+    const float *bias = nullptr;
+    int bias_per_row = 0;
+    const float *R = nullptr;
+    long ldr = 0, strideR = 0;
+    const unsigned char *mask = nullptr;
+    long strideMask = 0;
+    float *C = nullptr;
+    long ldc = 0, strideC = 0;
+    int M = 0, N = 0, K = 0, relu = 0;
+    int cblk = 0;             // > 0: C is stored column-block-major, [ceil(N / cblk)][M][cblk] (include/dfx_gemm.h)
+    long cblk_stride = 0;     // elements between column blocks (>= M * cblk)
+    long ablk_stride = 0;     // > 0: A is K-block-major, [K / 4][M][4] with this many elements between blocks
+    int wide_epilogue = 0;    // row-major C (and R) with 16-byte aligned rows, N % 4 == 0: float4 epilogue through LDS
+    int splits = 1, kper = 0; // split-K: z = batch * splits + split, split s covers k in [s * kper, min(K, (s + 1) * kper))
+    int nx = 0, ny = 0;       // tiles along N and M (the grid is one-dimensional: nx * ny * nz workgroups)
+    const float *B2 = nullptr;// two-segment [K,N] operand: rows k >= K1 come from B2 (row k - K1), same ldb; LDS-DMA path only
+    long strideB2 = 0;
+    int K1 = 0;
+    int group_m = 0;          // tile order (placement only, never results): 0 = n fastest, then m, then z, as dispatched;
+                              // > 0: workgroup ids are XCD-remapped (each XCD walks one contiguous range) and run m fastest inside
+                              // groups of group_m tile rows, then along the columns of every batch element
+    int fast_cblk = 0;        // column-block-major C through the same LDS round trip (set by launch())
+    int fast_epi = 0;         // wide epilogue in its lean form (set by launch(): no GELU, C and R slices < 2 GiB)
+    long strideBias = 0;      // elements the column bias advances per batch element (wide column blocks run as a batch: dfx_gemm_f32)
 };
 
-__device__ __forceinline__ float activate(float v, int act)      // 1: ReLU, 2: exact (erf) GELU
+// the product every entry point starts from: C[M,N] = A[M,K] x B, one K range, plain row-major C
+Args product(const float *A, long lda, const float *B, long ldb, float *C, long ldc, int M, int N, int K)
 {
-    return act == 1 ? fmaxf(v, 0.f) : 0.5f * v * (1.f + erff(v * 0.70710678118654752440f));
+    Args g;
+    g.A = A, g.lda = lda;
+    g.B = B, g.ldb = ldb;
+    g.C = C, g.ldc = ldc;
+    g.M = M, g.N = N, g.K = g.kper = K;
+    return g;
 }
 
 // waves per SIMD the register allocation must leave room for (HIP's second __launch_bounds__ argument; what the K loop's own
@@ -76,51 +77,89 @@ constexpr int min_blocks(int BM, int BN, int NW, int BK)
            : BM == 128 && BN == 64 ? 5 : BM == 64 && BN == 64 ? 6 : BM == 128 && BN == 96 ? 3 : BM == 128 && BN == 32 ? 6 : 1;
 }
 
+// tile (bx, by) of batch element / split bz that this workgroup computes (scalar arithmetic; see Args::group_m)
+__device__ __forceinline__ void tile_coords(const Args &g, int &bx, int &by, long &bz)
+{
+    int lin = blockIdx.x;
+    if (g.group_m > 0) {
+        lin = dfx::xcd_remap(lin, (int)gridDim.x);
+        const int nJ = (int)(gridDim.x / (unsigned)g.ny);           // columns of all batch elements
+        const int grp = lin / (g.group_m * nJ), y0 = grp * g.group_m;
+        const int gsz = min(g.ny - y0, g.group_m), r = lin - grp * g.group_m * nJ;
+        by = y0 + r % gsz;
+        const int J = r / gsz;
+        bx = J % g.nx;
+        bz = J / g.nx;
+    } else {
+        bx = lin % g.nx;
+        by = (lin / g.nx) % g.ny;
+        bz = lin / (g.nx * g.ny);
+    }
+}
+
+// Column-block-major C ([N / w][M][w], w = 4 or 12: what msda_level_forward reads) through the LDS round trip of the float4
+// epilogues: a pass's float4s are numbered block-major - (block, row, quad of the block), quad fastest - so that consecutive
+// lanes write consecutive memory (64 rows x w floats of one block per wave-instruction for w = 4) instead of one scattered
+// dword per lane and accumulator register.
+template <class T>
+__device__ __forceinline__ void epilogue_cblk(float *Ct, const f32x16 (&acc)[T::MT][T::NT], const Lane &l, int m0, int n0, const Epilogue &e)
+{
+    constexpr int NF4 = T::PR * T::CQ;                     // float4 per pass
+    const bool brow = e.bias && e.bias_per_row, bcol = e.bias && !e.bias_per_row;
+    const int QB = e.cblk >> 2, b0 = n0 / e.cblk;         // quads per block, first block of the tile
+    const __amdgpu_buffer_rsrc_t rsC = buffer(e.C, ((long)(e.N / e.cblk - 1) * e.cblk_stride + (long)e.M * e.cblk) * 4);
+#pragma unroll
+    for (int p = 0; p < T::BM / T::PR; ++p) {
+        if (p > 0) __syncthreads();
+        acc_to_lds<T>(Ct, acc, l, p);
+        __syncthreads();
+#pragma unroll
+        for (int e0 = 0; e0 < NF4; e0 += T::NTHR) {
+            const int f = e0 + l.tid;
+            if (NF4 % T::NTHR != 0 && f >= NF4) break;
+            const int blk = f / (T::PR * QB), rem = f - blk * (T::PR * QB), row = rem / QB, sub = rem - row * QB;
+            const int m = m0 + T::tile_row(p, row);
+            const int q = blk * QB + sub, n = n0 + q * 4;
+            f32x4 v = *reinterpret_cast<const f32x4 *>(&Ct[row * T::LDC + q * 4]);
+            const bool ok = m < e.M && n < e.N;
+            if (bcol) v += *reinterpret_cast<const f32x4 *>(e.bias + min(n, e.N - 4));
+            if (brow) v += e.bias[min(m, e.M - 1)];
+            if (e.act) relu4(v);
+            if (e.mask && e.mask[min(m, e.M - 1)]) v = (f32x4){0.f, 0.f, 0.f, 0.f};
+            store4(v, rsC, ok ? (unsigned)(((long)(b0 + blk) * e.cblk_stride + (long)m * e.cblk + sub * 4) * 4) : kOut);
+        }
+    }
+}
+
 template <int BM, int BN, int WM, int WN, bool B_KN, int BK, bool DMA>
 __global__ __launch_bounds__(64 * WM * WN, min_blocks(BM, BN, WM * WN, BK)) void gemm_f32_kernel(const Args g)
 {
-    constexpr int TM = BM / WM, TN = BN / WN, MT = TM / 32, NT = TN / 32;
+    using T = Tile<BM, BN, WM, WN, 64 * WM * WN>;
+    constexpr int MT = T::MT, NT = T::NT;
     constexpr int LDK = BK + 4;                       // [m][k] / [n][k] pitch: 5 (BK = 16) sixteen-byte slots
-    constexpr int LDB = BN + 4;                       // [k][n] pitch of the [K][N] operand (16-byte aligned rows)
+    constexpr int LDB = T::LDB;                       // [k][n] pitch of the [K][N] operand (16-byte aligned rows)
     constexpr int KQ = BK / 4;                        // float4 per row per K-step
-    constexpr int A_F4 = BM * KQ, B_F4 = BN * KQ;     // (= BK * BN / 4 for the [K][N] operand as well)     // float4 per K-step in the A / B tile
+    constexpr int BQ = B_KN ? BN / 4 : KQ;            // ... per row of the staged B image
+    constexpr int A_F4 = BM * KQ, B_F4 = BN * KQ;     // float4 per K-step in the A / B tile (= BK * BN / 4 for the [K][N] operand as well)
     constexpr int NW = WM * WN, NTHR = 64 * NW;       // waves / threads of the workgroup (4 / 256, or 8 / 512 for the 256 x 128 tile)
     constexpr int A_LOADS = (A_F4 + NTHR - 1) / NTHR; // ... per thread (last pass may be partial)
     constexpr int B_LOADS = (B_F4 + NTHR - 1) / NTHR;
-    static_assert((NW == 4 || NW == 8) && TM % 32 == 0 && TN % 32 == 0, "bad wave layout");
+    static_assert(NW == 4 || NW == 8, "bad wave layout");
     static_assert(BK % 8 == 0, "a ds_read_b128 covers 8 consecutive k (4 per lane half)");
-    // one LDS object: the two operand stages, re-used by the epilogue as a [64][BN + 4] transpose buffer
+    // one LDS object: the two operand stages, re-used by the epilogues as a [64][BN + 4] transpose buffer
     constexpr int A_SZ = BM * LDK, B_SZ = B_KN ? BK * LDB : BN * LDK;               // floats per stage
-    constexpr int PR = 64;                            // tile rows per epilogue pass through LDS
-    constexpr int LDC = BN + 4, C_SZ = PR * LDC;
+    constexpr int C_SZ = T::PR * T::LDC;
     constexpr int S_SZ = 2 * (A_SZ + B_SZ) > C_SZ ? 2 * (A_SZ + B_SZ) : C_SZ;
     __shared__ __attribute__((aligned(16))) float smem[S_SZ];
-    float (*const As)[BM][LDK] = reinterpret_cast<float (*)[BM][LDK]>(smem);        // As[buf][m][k]
-    float (*const Bs)[B_SZ] = reinterpret_cast<float (*)[B_SZ]>(smem + 2 * A_SZ);   // Bs[buf][...]: [k][n] or [n][k]
+    float (*const As)[A_SZ] = reinterpret_cast<float (*)[A_SZ]>(smem);              // As[buf]: [m][k]
+    float (*const Bs)[B_SZ] = reinterpret_cast<float (*)[B_SZ]>(smem + 2 * A_SZ);   // Bs[buf]: [k][n] or [n][k]
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave / WN, wn = wave % WN;
-    const int half = lane >> 5, c = lane & 31;
-    // tile of this workgroup (scalar arithmetic; see Args::group_m)
+    // ---- tile coordinates and this workgroup's slices of the operands ------------------------------------------------
+    const int tid = threadIdx.x, lane = tid & 63;
+    const Lane l = lane_of<T>(tid);
     int bx, by;
     long bz;
-    {
-        int lin = blockIdx.x;
-        if (g.group_m > 0) {
-            lin = dfx::xcd_remap(lin, (int)gridDim.x);
-            const int nJ = (int)(gridDim.x / (unsigned)g.ny);           // columns of all batch elements
-            const int grp = lin / (g.group_m * nJ), y0 = grp * g.group_m;
-            const int gsz = min(g.ny - y0, g.group_m), r = lin - grp * g.group_m * nJ;
-            by = y0 + r % gsz;
-            const int J = r / gsz;
-            bx = J % g.nx;
-            bz = J / g.nx;
-        } else {
-            bx = lin % g.nx;
-            by = (lin / g.nx) % g.ny;
-            bz = lin / (g.nx * g.ny);
-        }
-    }
+    tile_coords(g, bx, by, bz);
     const int m0 = by * BM, n0 = bx * BN;
     const long cz = bz;                                   // C slice: one per (batch, split)
     int kbeg = 0, K = g.K;                                // this workgroup's K range
@@ -135,50 +174,42 @@ __global__ __launch_bounds__(64 * WM * WN, min_blocks(BM, BN, WM * WN, BK)) void
     const float *A2 = g.A2 ? g.A2 + bz * g.strideA + ashift : nullptr;
     const float *B = g.B + bz * g.strideB + (B_KN ? (long)kbeg * g.ldb : (long)kbeg);
 
-    f32x16 acc[MT][NT];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    f32x16 acc[MT][NT] = {};
 
-    // Operand staging by buffer loads: one wave-uniform descriptor per operand whose size is the operand's exact
-    // extent, a 32-bit byte offset per lane that advances by a constant per K-step.  Rows / columns outside the
-    // problem get an offset beyond every extent (0x80000000; the host checks that an operand stays below 2 GiB),
-    // so the hardware's range check returns zeros for them - no clamps, no selects, no 64-bit address arithmetic in
-    // the loop.  K tails: rows of a [K][N] operand and blocks of a K-block-major A beyond K lie past the extent as
-    // well; for K-contiguous operands the last K-step masks its lanes (wave-uniform branch).
-    constexpr unsigned kOut = 0x80000000u;
+    // ---- operand staging by buffer loads --------------------------------------------------------------------------------
+    // One descriptor per operand whose size is the operand's exact extent, a 32-bit byte offset per lane that advances by
+    // a constant per K-step; rows / columns outside the problem get kOut (mfma_tile.h; the host checks that an operand
+    // stays below 2 GiB).  K tails: rows of a [K][N] operand and blocks of a K-block-major A beyond K lie past the extent
+    // as well; for K-contiguous operands the last K-step masks its lanes (wave-uniform branch).
     const long bytesA = g.ablk_stride > 0 ? ((long)(K / 4 - 1) * g.ablk_stride + (long)g.M * 4) * 4
                                           : ((long)(g.M - 1) * g.lda + K) * 4;
     const long bytesB = B_KN ? ((long)(K - 1) * g.ldb + g.N) * 4 : ((long)(g.N - 1) * g.ldb + K) * 4;
-    const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(A), 0, (int)bytesA, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsA2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(A2 ? A2 : A), 0, (int)bytesA, 0x00020000);
-    // (two-segment operand: this descriptor covers rows 0 .. K1 - 1, rsB2 the rest)
-    const long bytesB1 = (B_KN && g.B2) ? ((long)(g.K1 - 1) * g.ldb + g.N) * 4 : bytesB;
-    const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(B), 0, (int)bytesB1, 0x00020000);
-    const float *Bsec = (B_KN && g.B2) ? g.B2 + bz * g.strideB2 : B;
-    const __amdgpu_buffer_rsrc_t rsB2 = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float *>(Bsec), 0, (int)(((long)(g.K - g.K1 - 1) * g.ldb + g.N) * 4), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsA = buffer(A, bytesA), rsA2 = buffer(A2 ? A2 : A, bytesA);
+    // (two-segment operand: rsB covers rows 0 .. K1 - 1, rsB2 the rest)
+    const __amdgpu_buffer_rsrc_t rsB = buffer(B, (B_KN && g.B2) ? ((long)(g.K1 - 1) * g.ldb + g.N) * 4 : bytesB);
+    const __amdgpu_buffer_rsrc_t rsB2 = buffer((B_KN && g.B2) ? g.B2 + bz * g.strideB2 : B, ((long)(g.K - g.K1 - 1) * g.ldb + g.N) * 4);
+    // byte offset of float4 kq of tile row `row` of A; of float4 q of row r of the staged B image ([k][n]: r = k, else r = n)
+    auto a_off = [&](int row, int kq) {
+        const int m = m0 + row;
+        const unsigned o = g.ablk_stride > 0 ? ((unsigned)kq * (unsigned)g.ablk_stride + (unsigned)m * 4u) * 4u
+                                             : ((unsigned)m * (unsigned)g.lda + (unsigned)kq * 4u) * 4u;
+        return m < g.M ? o : kOut;
+    };
+    auto b_off = [&](int r, int q) {
+        const int n = B_KN ? n0 + q * 4 : n0 + r;
+        const unsigned o = B_KN ? ((unsigned)r * (unsigned)g.ldb + (unsigned)n) * 4u : ((unsigned)n * (unsigned)g.ldb + (unsigned)q * 4u) * 4u;
+        return n < g.N ? o : kOut;
+    };
     unsigned va[A_LOADS], vb[B_LOADS];
 #pragma unroll
     for (int i = 0; i < A_LOADS; ++i) {
-        const int f = tid + i * NTHR, row = f / KQ, kq = f % KQ, m = m0 + row;
-        const unsigned o = g.ablk_stride > 0 ? ((unsigned)kq * (unsigned)g.ablk_stride + (unsigned)m * 4u) * 4u
-                                             : ((unsigned)m * (unsigned)g.lda + (unsigned)kq * 4u) * 4u;
-        va[i] = (m < g.M && f < A_F4) ? o : kOut;
+        const int f = tid + i * NTHR;
+        va[i] = f < A_F4 ? a_off(f / KQ, f % KQ) : kOut;
     }
 #pragma unroll
     for (int i = 0; i < B_LOADS; ++i) {
         const int f = tid + i * NTHR;
-        if (B_KN) {
-            const int kr = f / (BN / 4), nq = f % (BN / 4), n = n0 + nq * 4;
-            vb[i] = (n < g.N && f < B_F4) ? ((unsigned)kr * (unsigned)g.ldb + (unsigned)n) * 4u : kOut;
-        } else {
-            const int row = f / KQ, kq = f % KQ, n = n0 + row;
-            vb[i] = (n < g.N && f < B_F4) ? ((unsigned)n * (unsigned)g.ldb + (unsigned)kq * 4u) * 4u : kOut;
-        }
+        vb[i] = f < B_F4 ? b_off(f / BQ, f % BQ) : kOut;
     }
     const unsigned stepA = g.ablk_stride > 0 ? (unsigned)(BK / 4) * (unsigned)g.ablk_stride * 4u : BK * 4u;
     const unsigned stepB = B_KN ? (unsigned)BK * (unsigned)g.ldb * 4u : BK * 4u;
@@ -192,13 +223,13 @@ __global__ __launch_bounds__(64 * WM * WN, min_blocks(BM, BN, WM * WN, BK)) void
         ktail_k0 = k0;
 #pragma unroll
         for (int i = 0; i < A_LOADS; ++i) {
-            ra[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsA, va[i], 0, 0));
-            if (A2) ra2[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsA2, va[i], 0, 0));
+            ra[i] = load4(rsA, va[i]);
+            if (A2) ra2[i] = load4(rsA2, va[i]);
             va[i] += stepA;
         }
 #pragma unroll
         for (int i = 0; i < B_LOADS; ++i) {
-            rb[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsB, vb[i], 0, 0));
+            rb[i] = load4(rsB, vb[i]);
             vb[i] += stepB;
         }
     };
@@ -210,21 +241,15 @@ __global__ __launch_bounds__(64 * WM * WN, min_blocks(BM, BN, WM * WN, BK)) void
             f32x4 v = ra[i];
             if (A2) v += ra2[i];
             if (ktail && g.ablk_stride == 0 && ktail_k0 + kq * 4 >= K) v = zero4;
-            *reinterpret_cast<f32x4 *>(&As[buf][row][kq * 4]) = v;
+            *reinterpret_cast<f32x4 *>(&As[buf][row * LDK + kq * 4]) = v;
         }
 #pragma unroll
         for (int i = 0; i < B_LOADS; ++i) {
-            const int f = tid + i * NTHR;
+            const int f = tid + i * NTHR, r = f / BQ, q = f % BQ;
             if (f >= B_F4) continue;
-            if (B_KN) {
-                const int kr = f / (BN / 4), nq = f % (BN / 4);
-                *reinterpret_cast<f32x4 *>(&Bs[buf][kr * LDB + nq * 4]) = rb[i];
-            } else {
-                const int row = f / KQ, kq = f % KQ;
-                f32x4 v = rb[i];
-                if (ktail && ktail_k0 + kq * 4 >= K) v = zero4;
-                *reinterpret_cast<f32x4 *>(&Bs[buf][row * LDK + kq * 4]) = v;
-            }
+            f32x4 v = rb[i];
+            if (!B_KN && ktail && ktail_k0 + q * 4 >= K) v = zero4;
+            *reinterpret_cast<f32x4 *>(&Bs[buf][r * (B_KN ? LDB : LDK) + q * 4]) = v;
         }
     };
 
@@ -232,18 +257,14 @@ __global__ __launch_bounds__(64 * WM * WN, min_blocks(BM, BN, WM * WN, BK)) void
     // epilogue's residual loads nothing to hide behind, so they are issued here, before the K loop, through a buffer
     // descriptor of the residual's exact extent (rows / columns outside the problem return zeros, never used).
     constexpr bool PREFETCH_R = BM == 64 && BN == 128;
-    constexpr int R_F4 = 64 * BN / 4 / 256;
-    f32x4 rpre[PREFETCH_R ? R_F4 : 1];
+    f32x4 rpre[PREFETCH_R ? T::NIT : 1];
     const bool use_rpre = PREFETCH_R && g.R && g.wide_epilogue;
     if (PREFETCH_R && use_rpre) {
-        const float *Rb = g.R + bz * g.strideR;
-        const __amdgpu_buffer_rsrc_t rsR = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(Rb), 0, (int)(((long)(g.M - 1) * g.ldr + g.N) * 4), 0x00020000);
+        const __amdgpu_buffer_rsrc_t rsR = buffer(g.R + bz * g.strideR, ((long)(g.M - 1) * g.ldr + g.N) * 4);
 #pragma unroll
-        for (int i = 0; i < R_F4; ++i) {
-            const int f = tid + i * 256, row = f / (BN / 4), c4 = f % (BN / 4);
-            const int m = m0 + row, n = n0 + c4 * 4;
-            const unsigned o = (m < g.M && n < g.N) ? ((unsigned)m * (unsigned)g.ldr + (unsigned)n) * 4u : 0x80000000u;
-            rpre[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsR, o, 0, 0));
+        for (int i = 0; i < T::NIT; ++i) {
+            const int f = tid + i * NTHR, m = m0 + f / T::CQ, n = n0 + f % T::CQ * 4;
+            rpre[PREFETCH_R ? i : 0] = load4(rsR, (m < g.M && n < g.N) ? ((unsigned)m * (unsigned)g.ldr + (unsigned)n) * 4u : kOut);
         }
     }
     // ---- LDS-DMA staging (DMA = true: no A2 prologue, K a multiple of BK) -------------------------------------------
@@ -257,55 +278,42 @@ __global__ __launch_bounds__(64 * WM * WN, min_blocks(BM, BN, WM * WN, BK)) void
     constexpr int A_SLOTS = BM * (LDK / 4), B_PITCH = B_KN ? LDB / 4 : LDK / 4, B_SLOTS = (B_KN ? BK : BN) * B_PITCH;
     constexpr int A_INSTR = (A_SLOTS + 63) / 64, B_INSTR = (B_SLOTS + 63) / 64;
     constexpr int A_PW = (A_INSTR + NW - 1) / NW, B_PW = (B_INSTR + NW - 1) / NW;
-    const int wave_u = __builtin_amdgcn_readfirstlane(wave);
+    const int wave_u = __builtin_amdgcn_readfirstlane(tid >> 6);
     unsigned dva[DMA ? A_PW : 1], dvb[DMA ? B_PW : 1];
     bool dpa[DMA ? A_PW : 1], dpb[DMA ? B_PW : 1];
     if (DMA) {
 #pragma unroll
         for (int i = 0; i < A_PW; ++i) {
-            const int sl = (wave_u + NW * i) * 64 + lane, row = sl / (LDK / 4), kq = min(sl % (LDK / 4), BK / 4 - 1), m = m0 + row;
+            const int sl = (wave_u + NW * i) * 64 + lane;
             dpa[i] = wave_u + NW * i < A_INSTR && sl < A_SLOTS;
-            const unsigned o = g.ablk_stride > 0 ? ((unsigned)kq * (unsigned)g.ablk_stride + (unsigned)m * 4u) * 4u
-                                                 : ((unsigned)m * (unsigned)g.lda + (unsigned)kq * 4u) * 4u;
-            dva[i] = m < g.M ? o : kOut;
+            dva[i] = a_off(sl / (LDK / 4), min(sl % (LDK / 4), KQ - 1));
         }
 #pragma unroll
         for (int i = 0; i < B_PW; ++i) {
             const int sl = (wave_u + NW * i) * 64 + lane;
             dpb[i] = wave_u + NW * i < B_INSTR && sl < B_SLOTS;
-            if (B_KN) {
-                const int kr = sl / B_PITCH, nq = min(sl % B_PITCH, BN / 4 - 1), n = n0 + nq * 4;
-                dvb[i] = n < g.N ? ((unsigned)kr * (unsigned)g.ldb + (unsigned)n) * 4u : kOut;
-            } else {
-                const int row = sl / B_PITCH, kq = min(sl % B_PITCH, BK / 4 - 1), n = n0 + row;
-                dvb[i] = n < g.N ? ((unsigned)n * (unsigned)g.ldb + (unsigned)kq * 4u) * 4u : kOut;
-            }
+            dvb[i] = b_off(sl / B_PITCH, min(sl % B_PITCH, BQ - 1));
         }
     }
     auto dma_tiles = [&](int k0, int buf) {
-#if defined(__HIP_DEVICE_COMPILE__)      // (the host pass cannot form an LDS-address-space pointer; it only needs the kernel's handle)
-        typedef __attribute__((address_space(3))) void *lds_ptr;
         const unsigned sa = g.ablk_stride > 0 ? (unsigned)(k0 >> 2) * (unsigned)g.ablk_stride * 4u : (unsigned)k0 * 4u;
         const bool second = B_KN && g.B2 && k0 >= g.K1;             // (scalar: a K-step lies in one segment, K1 % BK == 0)
         const unsigned sb = B_KN ? (unsigned)(second ? k0 - g.K1 : k0) * (unsigned)g.ldb * 4u : (unsigned)k0 * 4u;
-        float *la = &As[buf][0][0], *lb = &Bs[buf][0];
 #pragma unroll
         for (int i = 0; i < A_PW; ++i)
-            if (dpa[i]) __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (lds_ptr)(la + (wave_u + NW * i) * 256), 16, dva[i], sa, 0, 0);
+            if (dpa[i]) lds_dma16(rsA, As[buf] + (wave_u + NW * i) * 256, dva[i], sa);
         if (second) {
 #pragma unroll
             for (int i = 0; i < B_PW; ++i)
-                if (dpb[i]) __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB2, (lds_ptr)(lb + (wave_u + NW * i) * 256), 16, dvb[i], sb, 0, 0);
+                if (dpb[i]) lds_dma16(rsB2, Bs[buf] + (wave_u + NW * i) * 256, dvb[i], sb);
         } else {
 #pragma unroll
             for (int i = 0; i < B_PW; ++i)
-                if (dpb[i]) __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, (lds_ptr)(lb + (wave_u + NW * i) * 256), 16, dvb[i], sb, 0, 0);
+                if (dpb[i]) lds_dma16(rsB, Bs[buf] + (wave_u + NW * i) * 256, dvb[i], sb);
         }
-#else
-        (void)rsB2;
-#endif
     };
 
+    // ---- K loop -----------------------------------------------------------------------------------------------------------
     const int steps = (K + BK - 1) / BK;
     if (DMA) {
         dma_tiles(0, 0);
@@ -318,286 +326,30 @@ __global__ __launch_bounds__(64 * WM * WN, min_blocks(BM, BN, WM * WN, BK)) void
     for (int t = 0; t < steps; ++t) {
         const int buf = t & 1;
         if (!DMA && t + 1 < steps) load_tiles((t + 1) * BK);   // in flight during the MFMAs below
-        // A fragments (and B's for the [N][K] operand): one 16-byte read per lane per 4 MFMAs
-        constexpr int KJ = BK / 8;
-        float4 af[KJ][MT], bf[KJ][NT];
-#pragma unroll
-        for (int j = 0; j < KJ; ++j) {
-#pragma unroll
-            for (int i = 0; i < MT; ++i)
-                af[j][i] = *reinterpret_cast<const float4 *>(&As[buf][wm * TM + i * 32 + c][j * 8 + half * 4]);
-            if (!B_KN) {
-#pragma unroll
-                for (int jn = 0; jn < NT; ++jn)
-                    bf[j][jn] = *reinterpret_cast<const float4 *>(&Bs[buf][(wn * TN + jn * 32 + c) * LDK + j * 8 + half * 4]);
-            }
-        }
-        float bs[2][NT];                                        // [K][N] operand: scalar reads, one MFMA ahead
-        float bsa[DMA && B_KN ? BK / 2 : 1][NT];                // LDS-DMA staging: every fragment of the K-step up front
-        if (B_KN && !DMA) {
-#pragma unroll
-            for (int jn = 0; jn < NT; ++jn) bs[0][jn] = Bs[buf][(half * 4) * LDB + wn * TN + jn * 32 + c];
-        }
-        if (DMA) {
-            // hipcc orders every LDS read that follows an LDS-DMA in program order behind it (s_waitcnt vmcnt(0): it
-            // cannot tell the two buffers of the one LDS array apart), so the K-step's reads all come first and the
-            // next tile's DMA is issued after them: it then lands under the 8 x MT x NT MFMAs below.
-            if (B_KN) {
-#pragma unroll
-                for (int q = 0; q < BK / 2; ++q)
-#pragma unroll
-                    for (int jn = 0; jn < NT; ++jn)
-                        bsa[q][jn] = Bs[buf][((q >> 2) * 8 + half * 4 + (q & 3)) * LDB + wn * TN + jn * 32 + c];
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            if (t + 1 < steps) dma_tiles((t + 1) * BK, buf ^ 1);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-#pragma unroll
-        for (int q = 0; q < BK / 2; ++q) {
-            const int j = q >> 2, tt = q & 3, cur = q & 1, nxt = cur ^ 1;
-            if (B_KN && !DMA && q + 1 < BK / 2) {
-                const int kn = ((q + 1) >> 2) * 8 + half * 4 + ((q + 1) & 3);
-#pragma unroll
-                for (int jn = 0; jn < NT; ++jn) bs[nxt][jn] = Bs[buf][kn * LDB + wn * TN + jn * 32 + c];
-            }
-            // keep the LDS reads of the next MFMA group AHEAD of this group's MFMAs (left alone, the scheduler
-            // reuses the fragment registers and sinks the reads below the MFMAs, exposing their latency)
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int i = 0; i < MT; ++i) {
-                const float av = tt == 0 ? af[j][i].x : tt == 1 ? af[j][i].y : tt == 2 ? af[j][i].z : af[j][i].w;
-#pragma unroll
-                for (int jn = 0; jn < NT; ++jn) {
-                    const float bv = B_KN ? (DMA ? bsa[DMA ? q : 0][jn] : bs[cur][jn])
-                                          : (tt == 0 ? bf[j][jn].x : tt == 1 ? bf[j][jn].y : tt == 2 ? bf[j][jn].z : bf[j][jn].w);
-                    acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[i][jn], 0, 0, 0);
-                }
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
+        if constexpr (B_KN && !DMA) kstep_kn<T, BK>(As[buf], Bs[buf], l, acc);
+        else kstep_up_front<T, BK, B_KN>(As[buf], Bs[buf], l, acc, [&] { if (DMA && t + 1 < steps) dma_tiles((t + 1) * BK, buf ^ 1); });
         if (!DMA && t + 1 < steps) store_tiles(buf ^ 1);
         if (DMA) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's DMA pieces of the next tile have landed ...
         __syncthreads();                                        // ... and after the barrier so have everybody's
     }
 
-    // ---- epilogue ----
-    float *C = g.C + cz * g.strideC;
-    const float *R = g.R ? g.R + bz * g.strideR : nullptr;
-    const unsigned char *mask = g.mask ? g.mask + bz * g.strideMask : nullptr;
-    const bool brow = g.bias && g.bias_per_row, bcol = g.bias && !g.bias_per_row;
-    const float *const biasp = g.bias ? g.bias + bz * g.strideBias : nullptr;
-    constexpr int CQ = BN / 4;                                 // float4 per tile row
-    if constexpr (NTHR % CQ == 0) if (g.wide_epilogue && g.fast_epi) {
-        // The lean form of the wide epilogue below (same LDS round trip, same float4 rows).  An ablation that ends the tile
-        // after the K loop (profiles/r03_gemm_epilogue_ablation.txt) showed the epilogue costing 13-16 % of
-        // a K = 256 launch and 4-5 % of a K = 1024 one - its vector instructions take issue slots from the other resident
-        // workgroups' MFMAs - so it is cut to the instructions it needs:
-        //   every wave writes one 32-row tile per pass (was: half of the waves two tiles, the others idle);
-        //   a thread keeps its column quad (column bias loaded once) and its rows are m = (m0 + r0) + D(pass, it) with D known
-        //   at compile time, so a store / residual / row-bias offset is one add to a per-thread base; C, R, the row bias and
-        //   the row mask go through buffer descriptors of their exact extents: rows beyond M fall past the extent (loads
-        //   return 0, stores are dropped), columns beyond N start from an offset beyond everything - no compares, no selects;
-        //   the body is compiled per (bias kind, residual, mask) instead of selecting at run time; ReLU is one v_max each.
-        float *Ct = smem;
-        constexpr int TPP = PR / (32 * WM);                   // 32-row tiles a wave writes per pass (0: keep the row-range passes)
-        constexpr int TP1 = TPP >= 1 ? TPP : 1;
-        constexpr bool BAL = TPP >= 1 && PR == TPP * 32 * WM && MT % TP1 == 0;
-        constexpr int RS = NTHR / CQ, NIT = PR / RS;          // rows between a thread's float4s, float4s per thread and pass
-        static_assert(PR % RS == 0 && (!BAL || (32 * TP1) % RS == 0), "a pass is a whole number of thread rows");
-        const int c4 = tid % CQ, r0 = tid / CQ;
-        const int n = n0 + c4 * 4, mb = m0 + r0;
-        constexpr unsigned kPast = 0x80000000u;
-        const bool ncol = n < g.N;
-        const unsigned cbase = ncol ? ((unsigned)mb * (unsigned)g.ldc + (unsigned)n) * 4u : kPast;
-        const unsigned rbase_off = ncol ? ((unsigned)mb * (unsigned)g.ldr + (unsigned)n) * 4u : kPast;
-        const __amdgpu_buffer_rsrc_t rsC = __builtin_amdgcn_make_buffer_rsrc(C, 0, (int)(((long)(g.M - 1) * g.ldc + g.N) * 4), 0x00020000);
-        const __amdgpu_buffer_rsrc_t rsR = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(R ? R : C), 0, (int)(((long)(g.M - 1) * (R ? g.ldr : g.ldc) + g.N) * 4), 0x00020000);
-        const __amdgpu_buffer_rsrc_t rsBias = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(biasp ? biasp : C), 0, g.M * 4, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rsMask = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char *>(mask ? mask : reinterpret_cast<const unsigned char *>(C)), 0, g.M, 0x00020000);
-        const int relu = g.relu;
-        auto run = [&](auto bias_kind, auto has_r, auto has_mask) {
-            constexpr int BIAS = decltype(bias_kind)::value;          // 0 none, 1 per column, 2 per row
-            constexpr bool HAS_R = decltype(has_r)::value, HAS_MASK = decltype(has_mask)::value;
-            f32x4 bc = {0.f, 0.f, 0.f, 0.f};
-            if (BIAS == 1 && ncol) bc = *reinterpret_cast<const f32x4 *>(biasp + n);
-            const bool r_pre = HAS_R && PREFETCH_R && use_rpre;
-#pragma unroll
-            for (int p = 0; p < BM / PR; ++p) {
-                // the residual, row bias and mask of this pass on their way while the tile goes through LDS
-                f32x4 rr[HAS_R ? NIT : 1];
-                float br[BIAS == 2 ? NIT : 1];
-                unsigned char mk[HAS_MASK ? NIT : 1];
-#pragma unroll
-                for (int it = 0; it < NIT; ++it) {
-                    const int D = BAL ? ((it * RS) / (32 * TP1)) * TM + p * TP1 * 32 + (it * RS) % (32 * TP1) : p * PR + it * RS;
-                    if (HAS_R && !r_pre)
-                        rr[HAS_R ? it : 0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsR, rbase_off + (unsigned)D * (unsigned)g.ldr * 4u, 0, 0));
-                    if (BIAS == 2)
-                        br[BIAS == 2 ? it : 0] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsBias, (unsigned)(mb + D) * 4u, 0, 0));
-                    if (HAS_MASK)
-                        mk[HAS_MASK ? it : 0] = __builtin_amdgcn_raw_buffer_load_b8(rsMask, (unsigned)(mb + D), 0, 0);
-                }
-                if (p > 0) __syncthreads();
-#pragma unroll
-                for (int i = 0; i < MT; ++i) {
-                    if (BAL ? i / TP1 != p : (wm * TM + i * 32) / PR != p) continue;      // compile-time / wave-uniform
-                    const int rb = (BAL ? (wm * TPP + i % TP1) * 32 : wm * TM + i * 32 - p * PR) + 4 * half;
-#pragma unroll
-                    for (int r = 0; r < 16; ++r)
-#pragma unroll
-                        for (int j = 0; j < NT; ++j)
-                            Ct[(rb + (r & 3) + 8 * (r >> 2)) * LDC + wn * TN + j * 32 + c] = acc[i][j][r];
-                }
-                __syncthreads();
-#pragma unroll
-                for (int it = 0; it < NIT; ++it) {
-                    const int D = BAL ? ((it * RS) / (32 * TP1)) * TM + p * TP1 * 32 + (it * RS) % (32 * TP1) : p * PR + it * RS;
-                    if (m0 + D >= g.M) continue;               // (scalar: the whole thread row lies beyond the last row)
-                    f32x4 v = *reinterpret_cast<const f32x4 *>(&Ct[(r0 + it * RS) * LDC + c4 * 4]);
-                    if (BIAS == 1) v += bc;
-                    if (BIAS == 2) v += br[BIAS == 2 ? it : 0];
-                    if (HAS_R) v += r_pre ? rpre[PREFETCH_R ? it : 0] : rr[HAS_R ? it : 0];
-                    if (relu) {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) asm("v_max_f32 %0, 0, %1" : "=v"(v[e]) : "v"(v[e]));
-                    }
-                    if (HAS_MASK && mk[HAS_MASK ? it : 0]) v = (f32x4){0.f, 0.f, 0.f, 0.f};
-                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((__vector_size__(4 * sizeof(unsigned)))) unsigned, v), rsC,
-                                                           cbase + (unsigned)D * (unsigned)g.ldc * 4u, 0, 0);
-                }
-            }
-        };
-        using T = std::true_type;
-        using F = std::false_type;
-        using B0 = std::integral_constant<int, 0>;
-        using B1 = std::integral_constant<int, 1>;
-        using B2 = std::integral_constant<int, 2>;
-        auto with_bias = [&](auto has_r, auto has_mask) {
-            if (brow) run(B2{}, has_r, has_mask); else if (bcol) run(B1{}, has_r, has_mask); else run(B0{}, has_r, has_mask);
-        };
-        if (mask) { if (R) with_bias(T{}, T{}); else with_bias(F{}, T{}); }
-        else { if (R) with_bias(T{}, F{}); else with_bias(F{}, F{}); }
-        return;
-    }
-    if (g.cblk > 0 && g.fast_cblk) {
-        // Column-block-major C ([N / w][M][w], w = 4 or 12: what msda_level_forward reads) through the same LDS round trip: a
-        // pass's float4s are numbered block-major - (block, row, quad of the block), quad fastest - so that consecutive lanes
-        // write consecutive memory (64 rows x w floats of one block per wave-instruction for w = 4) instead of one scattered
-        // dword per lane and accumulator register.
-        float *Ct = smem;
-        constexpr int TPP = PR / (32 * WM), TP1 = TPP >= 1 ? TPP : 1;
-        constexpr bool BAL = TPP >= 1 && PR == TPP * 32 * WM && MT % TP1 == 0;
-        constexpr int NF4 = PR * CQ;                           // float4 per pass
-        const int QB = g.cblk >> 2, b0 = n0 / g.cblk;         // quads per block, first block of the tile
-        const __amdgpu_buffer_rsrc_t rsC = __builtin_amdgcn_make_buffer_rsrc(C, 0, (int)(((long)(g.N / g.cblk - 1) * g.cblk_stride + (long)g.M * g.cblk) * 4), 0x00020000);
-        const int relu = g.relu;
-#pragma unroll
-        for (int p = 0; p < BM / PR; ++p) {
-            if (p > 0) __syncthreads();
-#pragma unroll
-            for (int i = 0; i < MT; ++i) {
-                if (BAL ? i / TP1 != p : (wm * TM + i * 32) / PR != p) continue;
-                const int rb = (BAL ? (wm * TPP + i % TP1) * 32 : wm * TM + i * 32 - p * PR) + 4 * half;
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-#pragma unroll
-                    for (int j = 0; j < NT; ++j)
-                        Ct[(rb + (r & 3) + 8 * (r >> 2)) * LDC + wn * TN + j * 32 + c] = acc[i][j][r];
-            }
-            __syncthreads();
-#pragma unroll
-            for (int e0 = 0; e0 < NF4; e0 += NTHR) {
-                const int e = e0 + tid;
-                if (NF4 % NTHR != 0 && e >= NF4) break;
-                const int blk = e / (PR * QB), rem = e - blk * (PR * QB), row = rem / QB, sub = rem - row * QB;
-                const int m = BAL ? m0 + (row / (32 * TP1)) * TM + p * TP1 * 32 + row % (32 * TP1) : m0 + p * PR + row;
-                const int q = blk * QB + sub, n = n0 + q * 4;
-                f32x4 v = *reinterpret_cast<const f32x4 *>(&Ct[row * LDC + q * 4]);
-                const bool ok = m < g.M && n < g.N;
-                if (bcol) v += *reinterpret_cast<const f32x4 *>(biasp + min(n, g.N - 4));
-                if (brow) v += biasp[min(m, g.M - 1)];
-                if (relu) {
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) asm("v_max_f32 %0, 0, %1" : "=v"(v[u]) : "v"(v[u]));
-                }
-                if (mask && mask[min(m, g.M - 1)]) v = (f32x4){0.f, 0.f, 0.f, 0.f};
-                const unsigned o = ok ? (unsigned)(((long)(b0 + blk) * g.cblk_stride + (long)m * g.cblk + sub * 4) * 4) : 0x80000000u;
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((__vector_size__(4 * sizeof(unsigned)))) unsigned, v), rsC, o, 0, 0);
-            }
-        }
-        return;
-    }
-    if (g.wide_epilogue) {
-        // Row-major C with 16-byte aligned rows: the accumulators (a lane holds one column of 16 scattered rows) go
-        // through LDS, 64 tile rows at a time, and leave as float4 per lane - a wave-instruction then covers whole
-        // BN*4-byte row segments (512 B for BN = 128) of C and of the residual instead of 128-byte pieces, with a
-        // quarter of the memory instructions.  The convolutions with many output channels and a short K
-        // (Bottleneck.conv3 + residual) are bound by exactly this traffic.
-        float *Ct = smem;
-#pragma unroll
-        for (int p = 0; p < BM / PR; ++p) {
-            if (p > 0) __syncthreads();
-#pragma unroll
-            for (int i = 0; i < MT; ++i) {
-                if ((wm * TM + i * 32) / PR != p) continue;           // wave-uniform
-                const int rbase = wm * TM + i * 32 - p * PR + 4 * half;
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-#pragma unroll
-                    for (int j = 0; j < NT; ++j)
-                        Ct[(rbase + (r & 3) + 8 * (r >> 2)) * LDC + wn * TN + j * 32 + c] = acc[i][j][r];
-            }
-            __syncthreads();
-            constexpr int F4 = PR * BN / 4;
-#pragma unroll
-            for (int f0 = 0; f0 < F4; f0 += NTHR) {
-                const int f = f0 + tid;
-                if (F4 % NTHR != 0 && f >= F4) break;
-                const int row = f / (BN / 4), c4 = f % (BN / 4);
-                const int m = m0 + p * PR + row, n = n0 + c4 * 4;
-                if (m >= g.M || n >= g.N) continue;
-                float4 v = *reinterpret_cast<const float4 *>(&Ct[row * LDC + c4 * 4]);
-                if (brow) { const float b = biasp[m]; v.x += b; v.y += b; v.z += b; v.w += b; }
-                if (bcol) { const float4 b = *reinterpret_cast<const float4 *>(biasp + n); v.x += b.x; v.y += b.y; v.z += b.z; v.w += b.w; }
-                if (PREFETCH_R && use_rpre) { const f32x4 q = rpre[PREFETCH_R ? f0 / 256 : 0]; v.x += q[0]; v.y += q[1]; v.z += q[2]; v.w += q[3]; }
-                else if (R) { const float4 q = *reinterpret_cast<const float4 *>(R + (long)m * g.ldr + n); v.x += q.x; v.y += q.y; v.z += q.z; v.w += q.w; }
-                if (g.relu) { v.x = activate(v.x, g.relu); v.y = activate(v.y, g.relu); v.z = activate(v.z, g.relu); v.w = activate(v.w, g.relu); }
-                if (mask && mask[m]) v = make_float4(0.f, 0.f, 0.f, 0.f);
-                *reinterpret_cast<float4 *>(C + (long)m * g.ldc + n) = v;
-            }
-        }
-        return;
-    }
-    int ncol[NT];
-    float bcolv[NT];
-    long coff[NT];                                     // element offset of the column inside a C row
-    const long rowmul = g.cblk > 0 ? (long)g.cblk : g.ldc;
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-        ncol[j] = n0 + wn * TN + j * 32 + c;
-        const int nc = min(ncol[j], g.N - 1);
-        bcolv[j] = bcol ? biasp[nc] : 0.f;
-        coff[j] = g.cblk > 0 ? (long)(nc / g.cblk) * g.cblk_stride + nc % g.cblk : (long)nc;
-    }
-#pragma unroll
-    for (int i = 0; i < MT; ++i) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int m = m0 + wm * TM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-            const int mc = min(m, g.M - 1);                         // clamped: branch-free loads
-            const float rb = brow ? biasp[mc] : 0.f;
-            const bool rz = mask ? mask[mc] != 0 : false;
-#pragma unroll
-            for (int j = 0; j < NT; ++j) {
-                float v = acc[i][j][r] + bcolv[j] + rb;
-                if (R) v += R[(long)mc * g.ldr + min(ncol[j], g.N - 1)];
-                if (g.relu) v = activate(v, g.relu);
-                if (rz) v = 0.f;
-                if (m < g.M && ncol[j] < g.N) C[(long)m * rowmul + coff[j]] = v;
-            }
-        }
-    }
+    // ---- epilogue dispatch (mfma_tile.h) ----------------------------------------------------------------------------------
+    // (the lane's coordinates are taken from the thread id again: the ones above would otherwise stay in registers through the K
+    // loop for the epilogue's sake, and the 256 x 128 tile with a K tail has none to spare)
+    int tid_e = threadIdx.x;
+    asm volatile("" : "+v"(tid_e));
+    const Lane le = lane_of<T>(tid_e);
+    Epilogue e;
+    e.C = g.C + cz * g.strideC, e.ldc = g.ldc;
+    e.R = g.R ? g.R + bz * g.strideR : nullptr, e.ldr = g.ldr;
+    e.bias = g.bias ? g.bias + bz * g.strideBias : nullptr, e.bias_per_row = g.bias_per_row;
+    e.mask = g.mask ? g.mask + bz * g.strideMask : nullptr;
+    e.M = g.M, e.N = g.N, e.act = g.relu;
+    e.cblk = g.cblk, e.cblk_stride = g.cblk_stride;
+    if constexpr (T::LEAN) if (g.wide_epilogue && g.fast_epi) return epilogue_lean_any<T, PREFETCH_R>(smem, acc, le, m0, n0, e, rpre, use_rpre);
+    if (g.cblk > 0 && g.fast_cblk) return epilogue_cblk<T>(smem, acc, le, m0, n0, e);      // (launch(): ReLU or no activation)
+    if (g.wide_epilogue) return epilogue_float4<T, PREFETCH_R>(smem, acc, le, m0, n0, e, rpre, use_rpre);
+    epilogue_scalar<T>(acc, le, m0, n0, e);
 }
 
 // Tile order of a launch (Args::group_m, read from DFX_GEMM_GROUP): every XCD walks one contiguous range of tiles, 8 tile rows at
@@ -658,10 +410,9 @@ __global__ __launch_bounds__(64 * NW) void linear_rows_kernel(const Args g)
     const int c = lane & 31, h = lane >> 5;
     const int bx = blockIdx.x % g.nx, by = blockIdx.x / g.nx;
     const int m0 = by * 32, n0 = bx * 32;
-    constexpr unsigned kOut = 0x80000000u;
-    const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(g.A), 0, (int)(((long)(g.M - 1) * g.lda + g.K) * 4), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsA2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(g.A2 ? g.A2 : g.A), 0, (int)(((long)(g.M - 1) * g.lda + g.K) * 4), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(g.B), 0, (int)(((long)(g.N - 1) * g.ldb + g.K) * 4), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsA = buffer(g.A, ((long)(g.M - 1) * g.lda + g.K) * 4);
+    const __amdgpu_buffer_rsrc_t rsA2 = buffer(g.A2 ? g.A2 : g.A, ((long)(g.M - 1) * g.lda + g.K) * 4);
+    const __amdgpu_buffer_rsrc_t rsB = buffer(g.B, ((long)(g.N - 1) * g.ldb + g.K) * 4);
     const int kw = wave * (CH * 64) + 32 * h;                      // first k of this lane in chunk 0
     const unsigned oa = m0 + c < g.M ? ((unsigned)(m0 + c) * (unsigned)g.lda + (unsigned)kw) * 4u : kOut;
     const unsigned ob = n0 + c < g.N ? ((unsigned)(n0 + c) * (unsigned)g.ldb + (unsigned)kw) * 4u : kOut;
@@ -670,15 +421,15 @@ __global__ __launch_bounds__(64 * NW) void linear_rows_kernel(const Args g)
     for (int ch = 0; ch < CH; ++ch)
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            a[ch][j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsA, oa, (ch * 64 + j * 4) * 4, 0));
-            b[ch][j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsB, ob, (ch * 64 + j * 4) * 4, 0));
+            a[ch][j] = load4(rsA, oa, (ch * 64 + j * 4) * 4);
+            b[ch][j] = load4(rsB, ob, (ch * 64 + j * 4) * 4);
         }
     if (g.A2) {
 #pragma unroll
         for (int ch = 0; ch < CH; ++ch)
 #pragma unroll
             for (int j = 0; j < 8; ++j)
-                a[ch][j] += __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsA2, oa, (ch * 64 + j * 4) * 4, 0));
+                a[ch][j] += load4(rsA2, oa, (ch * 64 + j * 4) * 4);
     }
     f32x16 acc;
 #pragma unroll
@@ -690,7 +441,7 @@ __global__ __launch_bounds__(64 * NW) void linear_rows_kernel(const Args g)
 #pragma unroll
             for (int t = 0; t < 4; ++t) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[ch][j][t], b[ch][j][t], acc, 0, 0, 0);
 #pragma unroll
-    for (int r = 0; r < 16; ++r) red[wave][(r & 3) + 8 * (r >> 2) + 4 * h][c] = acc[r];
+    for (int r = 0; r < 16; ++r) red[wave][acc_row(r, h)][c] = acc[r];
     __syncthreads();
     if (tid < 256) {
         const int row = tid >> 3, c4 = (tid & 7) * 4;
@@ -780,16 +531,25 @@ extern "C" int dfx_gemm_f32(const float *A, const float *A2, long lda, long stri
         // product of its own on the same A.  They run as ONE launch over the batch axis - A fixed, W / the column bias / C
         // advancing per block - in the XCD-aware tile order, which walks the columns of ALL blocks for a group of tile rows
         // before it moves on: an A panel is read once for the whole stack.
-        Args g{A, A2, lda, 0, B, ldb, (long)c_block * ldb, bias, bias_per_row, nullptr, 0, 0, row_mask, 0, C, (long)c_block, c_block_stride,
-               M, c_block, K, relu, 0, 0, 0, 1, 1, K};
-        g.strideBias = bias_per_row ? 0 : c_block;
+        Args g = product(A, lda, B, ldb, C, c_block, M, c_block, K);
+        g.A2 = A2;
+        g.strideB = (long)c_block * ldb, g.strideC = c_block_stride;
+        g.bias = bias, g.bias_per_row = bias_per_row, g.strideBias = bias_per_row ? 0 : c_block;
+        g.mask = row_mask;
+        g.relu = relu, g.wide_epilogue = 1;
         return choose_and_launch(g, N / c_block, 0, static_cast<hipStream_t>(stream));
     }
     const int wide = c_block == 0 && (N & 3) == 0 && (ldc & 3) == 0 && (strideC & 3) == 0 && dfx::aligned16(C) &&
                      (!R || ((ldr & 3) == 0 && (strideR & 3) == 0 && dfx::aligned16(R))) &&
                      (!bias || bias_per_row || dfx::aligned16(bias));
-    Args g{A, A2, lda, strideA, B, ldb, strideB, bias, bias_per_row, R, ldr, strideR, row_mask, strideMask, C, ldc, strideC,
-           M, N, K, relu, c_block, c_block_stride, a_block_stride, wide, 1, K};
+    Args g = product(A, lda, B, ldb, C, ldc, M, N, K);
+    g.A2 = A2;
+    g.strideA = strideA, g.strideB = strideB, g.strideC = strideC;
+    g.bias = bias, g.bias_per_row = bias_per_row;
+    g.R = R, g.ldr = ldr, g.strideR = strideR;
+    g.mask = row_mask, g.strideMask = strideMask;
+    g.relu = relu, g.wide_epilogue = wide;
+    g.cblk = c_block, g.cblk_stride = c_block_stride, g.ablk_stride = a_block_stride;
     return choose_and_launch(g, batch, b_is_kn, static_cast<hipStream_t>(stream));
 }
 
@@ -809,11 +569,11 @@ extern "C" int dfx_conv1x1_pair_f32(const float *W, const float *X1, long stride
         return dfx::fail(DFX_EINVAL, "conv1x1_pair: channel counts must be multiples of 16, H*W of 4, buffers 16-byte aligned");
     if (batch > 65535 || (long)Co * K * 4 >= (1L << 31) || (long)K1 * HW * 4 >= (1L << 31) || (long)K2 * HW * 4 >= (1L << 31))
         return dfx::fail(DFX_ERANGE, "conv1x1_pair: an operand exceeds 2 GiB per image");
-    Args g{W, nullptr, (long)K, 0, X1, (long)HW, strideX1, bias, 1, nullptr, 0, 0, nullptr, 0, Y, (long)HW, strideY,
-           Co, HW, K, act, 0, 0, 0, 1, 1, K};
-    g.B2 = X2;
-    g.strideB2 = strideX2;
-    g.K1 = K1;
+    Args g = product(W, K, X1, HW, Y, HW, Co, HW, K);
+    g.strideB = strideX1, g.strideC = strideY;
+    g.B2 = X2, g.strideB2 = strideX2, g.K1 = K1;
+    g.bias = bias, g.bias_per_row = 1;
+    g.relu = act, g.wide_epilogue = 1;
     return choose_and_launch(g, batch, 1, static_cast<hipStream_t>(stream));
 }
 
@@ -925,8 +685,10 @@ extern "C" int dfx_gemm_splitk_f32(const float *A, long lda, const float *B, lon
     int kper = ((K + splits - 1) / splits + 15) / 16 * 16;          // whole K-steps per split
     splits = (K + kper - 1) / kper;
     if (splits > 65535) return dfx::fail(DFX_ERANGE, "gemm_splitk: too many splits");
-    Args g{A, nullptr, lda, 0, B, ldb, 0, nullptr, 0, nullptr, 0, 0, nullptr, 0, workspace, (long)N, (long)M * N,
-           M, N, K, 0, 0, 0, 0, 1, splits, kper};
+    Args g = product(A, lda, B, ldb, workspace, N, M, N, K);
+    g.strideC = (long)M * N;                                       // one workspace slice per split
+    g.wide_epilogue = 1;
+    g.splits = splits, g.kper = kper;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int rc = choose_and_launch(g, 1, b_is_kn, st);
     if (rc != DFX_OK) return rc;

@@ -110,7 +110,7 @@ __global__ __launch_bounds__(64 * WAVES * GROUPS) void mha_fwd(const float *__re
         if (j0 + TK > Lk) {                                            // (scalar: only the last tile has keys to mask)
 #pragma unroll
             for (int r = 0; r < 16; ++r)
-                if (j0 + (r & 3) + 8 * (r >> 2) + 4 * half >= Lk) s[r] = -INFINITY;
+                if (j0 + acc_row(r, half) >= Lk) s[r] = -INFINITY;
         }
         float tmax = s[0];
 #pragma unroll
@@ -137,7 +137,7 @@ __global__ __launch_bounds__(64 * WAVES * GROUPS) void mha_fwd(const float *__re
         // ---- O^T += V^T P^T: MFMA r pairs key (r&3)+8(r>>2) (+4 for lane half 1) with p[r] ----
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const float va = vs[(r & 3) + 8 * (r >> 2) + 4 * half][col];
+            const float va = vs[acc_row(r, half)][col];
             o = __builtin_amdgcn_mfma_f32_32x32x2f32(va, s[r], o, 0, 0, 0);
         }
     }

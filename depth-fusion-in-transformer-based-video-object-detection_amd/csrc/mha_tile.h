@@ -2,19 +2,18 @@
 // dropout mask by a lane that owns a QUERY (4 consecutive keys of its mask row per accumulator register group).
 #pragma once
 #include <hip/hip_runtime.h>
+#include "mfma_tile.h"
 
 namespace dfx_mha {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
+using dfx::mfma::f32x16;
+using dfx::mfma::acc_row;     // row of accumulator register r in lane half h
 constexpr int D = 32;          // head dimension
 constexpr int TK = 32;         // rows (keys or queries) per tile
 constexpr int KP = 36;         // tile row pitch (floats): 9 sixteen-byte slots, conflict-free ds_read_b128
 constexpr int WAVES = 2;       // 64 queries (or keys) per workgroup
 constexpr float LOG2E = 1.44269504088896340736f;
 constexpr float LN2 = 0.69314718055994530942f;
-
-// row of accumulator register r in lane half h (the 32x32 MFMA accumulator layout)
-__device__ __forceinline__ int acc_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
 
 // mask values of keys key0 .. key0+3 (p points at key0 of the lane's mask row); keys past Lk read as 0.
 // vec: Lk % 4 == 0, so key0 (a multiple of 4) is 16-byte aligned in its row and the four keys are all in or all out.

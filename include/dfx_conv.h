@@ -41,7 +41,7 @@ int dfx_conv2d_igemm_f32(const float *x, const float *wp, const int *ktab, const
                          int stride, int pad, int dilation, int act, long x_image_stride, void *stream);
 
 /* Direct convolution of FEW input channels (Ci * KH * KW <= 160, Co <= 64, stride 1 or 2, no dilation) from an
- * LDS-resident input tile: the whole receptive field of a 16 x 16 output tile is staged once and the gathered
+ * LDS-resident input tile: the whole receptive field of an 8 x 32 output tile is staged once and the gathered
  * [K x pixels] operand of the fp32 MFMA is read from LDS (csrc/conv_tile.hip) - the 7x7/2 ResNet stem
  * (/root/reference/models/backbone_scratch.py:102-141 -> torchvision resnet conv1) and the first convolution of
  * the DFormer depth stem (/root/reference/models/dformer_backbone.py:18-71).  Operands as dfx_conv2d_igemm_f32

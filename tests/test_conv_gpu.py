@@ -28,6 +28,13 @@ CASES = [  # N, Ci, Co, H, W, k, stride, pad, dil, act
     (2, 32, 64, 21, 33, 3, 2, 1, 1, None),
     (1, 24, 40, 9, 11, 5, 1, 2, 1, "relu"),        # odd everything
     (1, 8, 200, 6, 7, 1, 1, 0, 1, None),           # 1x1, Co not a multiple of the tile
+    # BM = 128 needs Co % 128 == 0 and 512 tiles of 128 x 128: the smallest that qualify, through each epilogue (csrc/mfma_tile.h)
+    (4, 16, 128, 128, 128, 3, 1, 1, 1, "relu"),    # BM = 128, one tap per K-step, lean float4 epilogue
+    (4, 8, 128, 128, 128, 3, 1, 1, 1, "relu"),     # BM = 128, a tap per k
+    (4, 16, 128, 128, 128, 3, 1, 1, 1, "gelu"),    # general float4 epilogue
+    (5, 16, 128, 127, 127, 3, 1, 1, 1, None),      # BM = 128, an odd number of pixels: scalar epilogue
+    (1, 16, 72, 12, 14, 3, 1, 1, 1, "relu"),       # BM = 64, lean epilogue with tile rows beyond Co
+    (1, 16, 72, 12, 14, 3, 1, 1, 1, "gelu"),       # ... and the general one
 ]
 
 
