@@ -56,6 +56,8 @@ SIGNATURES = {
     "dfx_conv1x1_pair_f32": [_p, _p, _l, _i, _p, _l, _i, _p, _p, _l, _i, _i, _i, _i, _p],
     # W3, X1, stride, K1, X2, stride, K2, b3, R, stride, Y, stride, W1, b1, Z, stride, Co, C1, HW, batch, act_z, stream
     "dfx_conv1x1_chain_f32": [_p, _p, _l, _i, _p, _l, _i, _p, _p, _l, _p, _l, _p, _p, _p, _l, _i, _i, _i, _i, _i, _p],
+    # dY, ldy, X, ldx, dW, ldw, db | NULL, M, N, K, splits, workspace | NULL, stream (csrc/gemm_wgrad.hip)
+    "dfx_gemm_wgrad_f32": [_p, _l, _p, _l, _p, _l, _p, _i, _i, _i, _i, _p, _p],
     # include/dfx_fused.h: x, bias, residual, out, N, C, HW, relu, stream
     "dfx_bias_act_nchw_f32": [_p, _p, _p, _p, _i, _i, _l, _i, _p],
     "dfx_bias_relu_maxpool_f32": [_p, _p, _p, _i, _i, _i, _i, _p],

@@ -690,6 +690,105 @@ def linear(x, weight, bias=None, relu=False, residual=None, add=None, row_mask=N
     return out
 
 
+# ---- Linear in grad mode (include/dfx_gemm.h, dfx_gemm_wgrad_f32; csrc/gemm_wgrad.hip) ------------------------------------------
+# The split rule's two constants, both measured (tools/bench_linear_train.py, profiles/r14_linear_train.txt): ranges of at
+# least 16 row steps are 5-9 % ahead of 32-step ranges at 9600 rows (36 ranges against 18) and tie elsewhere; beyond ~256
+# ranges the reduction's traffic costs more than the shorter ranges save (32 x 4200 rows, N <= 128: 382-495 ranges 7-29 %
+# behind 255).  DFX_WGRAD_MIN_STEPS / DFX_WGRAD_MAX_RANGES are A/B aids.
+_WGRAD_MIN_STEPS = int(os.environ.get("DFX_WGRAD_MIN_STEPS", "16"))
+_WGRAD_MAX_RANGES = int(os.environ.get("DFX_WGRAD_MAX_RANGES", "256"))
+
+
+def _wgrad_ranges(M, splits):
+    """(rows per range, ranges) the library makes of a request for ``splits`` ranges over M rows: whole 16-row steps, none empty."""
+    kper = ((M + splits - 1) // splits + 15) // 16 * 16
+    return kper, (M + kper - 1) // kper
+
+
+def _wgrad_splits(M, N, K):
+    """Number of row ranges of the weight gradient dW[N,K] = dY[M,N]^T x[M,K] (pure host rule, ``_split_k``'s): the output has
+    only ceil(N / 128) * ceil(K / 128) tiles (one 64-row tile for N <= 64), so the M rows are cut into as many ranges as keep
+    tiles x ranges within one resident round of workgroups (3 per CU for the 128 x 128 tile, 4 for the 64 x 128 one), each at
+    least ``_WGRAD_MIN_STEPS`` 16-row steps long, at most ``_WGRAD_MAX_RANGES`` of them.  The result is what the library
+    will run: no range is empty."""
+    if M <= 0:
+        return 1
+    if N <= 64:
+        tiles, slots = -(-K // 128), 1024
+    else:
+        tiles, slots = -(-N // 128) * -(-K // 128), 768
+    want = max(1, min(-(-M // 16) // _WGRAD_MIN_STEPS, slots // tiles, _WGRAD_MAX_RANGES, 65535))
+    return _wgrad_ranges(M, want)[1]
+
+
+def linear_backward(grad_out, x, weight, need_x=True, need_w=True, need_b=True, splits=None):
+    """Gradients of ``y = linear(x, weight, bias)``: -> (grad_x | None, grad_w | None, grad_b | None), fp32, fresh tensors.
+    grad_out [..., N], x [..., K] contiguous, weight [N, K]; N and K multiples of 4.
+    grad_x = grad_out @ weight is ``dfx_gemm_f32`` with the weight as its [K,N] operand, in the row ranges ``linear`` uses for
+    operands of 2 GiB and more.  grad_w = grad_out^T @ x and grad_b = grad_out.sum(0) come from one ``dfx_gemm_wgrad_f32``
+    call (split over the rows by ``_wgrad_splits``, or ``splits``; partial sums are added in a fixed order: two calls give
+    the same bits).  ``need_w=False`` makes no weight-gradient launch; a bias gradient on its own (rare: a frozen weight
+    with a trained bias) is ``grad_out.sum(0)`` of the library."""
+    N, K = weight.shape
+    go, x2 = grad_out.reshape(-1, N), x.reshape(-1, K)
+    M = go.shape[0]
+    _check_inputs([("grad_out", go), ("x", x2), ("weight", weight)])
+    _require(go.dtype == torch.float32 and x2.dtype == torch.float32 and weight.dtype == torch.float32,
+             "linear_backward is implemented for float32")
+    _require(x2.shape[0] == M and N % 4 == 0 and K % 4 == 0, "linear_backward: grad_out [M,N], x [M,K] with N and K multiples of 4")
+    dev = x.device
+    grad_x = grad_w = grad_b = None
+    if need_x:
+        grad_x = torch.empty(x.shape, dtype=torch.float32, device=dev)
+        rows_max = max(128, (_GEMM_MAX_BYTES - 1) // (4 * max(N, K)) // 128 * 128)
+        for r0 in range(0, M, rows_max):
+            r1 = min(M, r0 + rows_max)
+            _call("linear_backward (grad_x)", "dfx_gemm_f32", dev, go.data_ptr() + r0 * N * 4, 0, N, 0, weight.data_ptr(), K, 0, 1,
+                  0, 0, 0, 0, 0, 0, 0, grad_x.data_ptr() + r0 * K * 4, K, 0, r1 - r0, K, N, 1, 0, 0, 0, 0)
+    if need_w:
+        grad_w = torch.empty((N, K), dtype=torch.float32, device=dev)
+        grad_b = torch.empty((N,), dtype=torch.float32, device=dev) if need_b else None
+        n = _wgrad_splits(M, N, K) if splits is None else int(splits)
+        ws = torch.empty((n * (N * K + N),), dtype=torch.float32, device=dev) if n > 1 else None
+        _call("linear_backward (grad_w)", "dfx_gemm_wgrad_f32", dev, go.data_ptr(), N, x2.data_ptr(), K, grad_w.data_ptr(), K,
+              _ptr(grad_b), M, N, K, n, _ptr(ws))
+    elif need_b:
+        grad_b = go.sum(0)
+    return grad_x, grad_w, grad_b
+
+
+# The node's forward is the function above, bound here: what a module calls by name (``ops.linear``, ``ops.linear_train``) is
+# its route and can be wrapped or recorded as such; the product inside the autograd node is not a route of its own.
+_linear_forward = linear
+
+
+class _LinearFunction(torch.autograd.Function):
+    """apply(x, weight, bias | None): saves the contiguous x and the weight, as nn.Linear does."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        ctx.save_for_backward(x, weight)
+        return _linear_forward(x, weight, bias)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        x, weight = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        # (looked up at call time: tests wrap it)
+        return linear_backward(grad_output.contiguous(), x, weight, need_x=need[0], need_w=need[1], need_b=need[2])
+
+
+def linear_train(x, weight, bias=None):
+    """``linear(x, weight, bias)`` that trains: with grad mode on and x, weight or bias requiring a gradient the result carries
+    it back through ``linear_backward`` - computed for exactly the inputs that ask for one; otherwise no autograd node is
+    made.  Either way the forward is ``linear`` itself (the same bits).  N and K multiples of 4."""
+    if torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad or (bias is not None and bias.requires_grad)):
+        _require(weight.shape[0] % 4 == 0 and weight.shape[1] % 4 == 0, "linear_train: N and K must be multiples of 4")
+        return _LinearFunction.apply(x.contiguous(), weight, bias)
+    return linear(x, weight, bias)
+
+
 def conv1x1(x, weight, bias=None, residual=None, relu=False, stride=1):
     """1x1 convolution on NCHW as a batched GEMM W[Co,Ci] x X_n[Ci,HW] with the folded-BN bias,
     the residual add and ReLU fused into the epilogue.  x [N,Ci,H,W], weight [Co,Ci(,1,1)]."""

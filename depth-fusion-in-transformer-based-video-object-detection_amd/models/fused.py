@@ -17,21 +17,40 @@ def enable_fused_inference(model, enabled=True):
     return n
 
 
+import os
+
 import torch
 from torch import nn
 
+# Linear in grad mode on the MFMA GEMM and its weight-gradient kernel (dfx.ops.linear_train, csrc/gemm_wgrad.hip);
+# DFX_LINEAR_TRAIN=0 keeps nn.Linear there (A/B measurements).  Read once at import.
+LINEAR_TRAIN = os.environ.get("DFX_LINEAR_TRAIN", "1") != "0"
+# The widest layer the route takes: out_features up to 1024 (the FFN) is what was measured and what the operator tests cover.
+# The input gradient adds its out_features terms one after the other in one MFMA chain; at RCNNHead's dynamic_layer
+# (256 -> 32768) that sum is 5.0e-6 from fp64 against the 2.3e-6 tests/test_dynconv_backward_gpu.py allows (4 x the CPU's
+# blocked fp32 sum), so wider layers stay on nn.Linear (profiles/r14_linear_train.txt).
+LINEAR_TRAIN_MAX_OUT_FEATURES = 1024
+
 
 class Linear(nn.Linear):
-    """nn.Linear (same parameters, same state_dict keys) whose no-grad fp32 forward on the GPU is the hand-written
-    MFMA GEMM with the bias in its epilogue (dfx.ops.linear, csrc/gemm_f32.hip); anything else is nn.Linear."""
+    """nn.Linear (same parameters, same state_dict keys) whose fp32 forward on the GPU is the hand-written MFMA GEMM with the
+    bias in its epilogue (dfx.ops.linear, csrc/gemm_f32.hip).  In grad mode, when the input or a parameter asks for a
+    gradient and out_features is a multiple of 4 (up to LINEAR_TRAIN_MAX_OUT_FEATURES) as well, the same forward carries an autograd node whose backward is the
+    GEMM again (input gradient) and csrc/gemm_wgrad.hip (weight and bias gradients): dfx.ops.linear_train.  Anything else
+    is nn.Linear."""
 
     def forward(self, x):
         # (under autocast, or with parameters in another dtype / on another device, this is plain nn.Linear)
-        if (x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled() and self.in_features % 4 == 0
+        if (x.is_cuda and x.dtype == torch.float32 and self.in_features % 4 == 0
                 and x.numel() > 0 and self.weight.dtype == torch.float32 and self.weight.device == x.device
                 and not torch.is_autocast_enabled()):
-            from dfx import ops
-            return ops.linear(x.contiguous(), self.weight, self.bias)
+            if not torch.is_grad_enabled():
+                from dfx import ops
+                return ops.linear(x.contiguous(), self.weight, self.bias)
+            if (LINEAR_TRAIN and self.out_features % 4 == 0 and self.out_features <= LINEAR_TRAIN_MAX_OUT_FEATURES
+                    and (x.requires_grad or self.weight.requires_grad or (self.bias is not None and self.bias.requires_grad))):
+                from dfx import ops
+                return ops.linear_train(x, self.weight, self.bias)
         return super().forward(x)
 
 

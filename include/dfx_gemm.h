@@ -62,6 +62,20 @@
  * activation panel and the Z accumulators of a wave live in registers), HW a multiple of 4; any other shape returns
  * DFX_EINVAL without a launch and the caller runs the two products as separate calls.  Y and Z are bit-equal to
  * dfx_gemm_f32 / dfx_conv1x1_pair_f32 followed by dfx_gemm_f32 on the same operands (same k order, same epilogue order).
+ *
+ * dfx_gemm_wgrad_f32: the weight and bias gradients of y = x W^T + b (csrc/gemm_wgrad.hip), what autograd computes for the
+ * nn.Linear layers listed above when they train:
+ *   dW[n][k] = sum_m dY[m][n] X[m][k]     [N, K], row pitch ldw
+ *   db[n]    = sum_m dY[m][n]             [N]; db may be NULL and is then not computed
+ * dY [M, N] (ldy) and X [M, K] (ldx) row-major: both operands are k-major for this product, whose summed dimension is the row
+ * count M.  Exact fp32 MFMA.  The outputs are overwritten, never accumulated into.  M is cut into ``splits`` ranges of whole
+ * 16-row steps (``splits`` is clamped so that no range is empty); with more than one range the partial results go to
+ * ``workspace`` (splits * (N * K + N) floats, caller-owned, 16-byte aligned) and one reduction launch adds them in ascending
+ * range order: no atomics, two calls give the same bits.  One range stores directly and ``workspace`` may be NULL.  db comes
+ * from the dY values the product stages anyway: no second pass over dY.
+ * N, K, ldy, ldx and ldw multiples of 4 (ld >= the row), dY, X, dW and workspace 16-byte aligned, else DFX_EINVAL.  Only one
+ * range has to stay below 2 GiB (rows per range * max(ldy, ldx) * 4 bytes, else DFX_ERANGE); the operands may be larger.
+ * N * K == 0 returns DFX_OK without a launch; M == 0 writes zeros to dW and db.
  */
 #ifndef DFX_GEMM_H
 #define DFX_GEMM_H
@@ -93,6 +107,10 @@ int dfx_conv1x1_chain_f32(const float *W3, const float *X1, long strideX1, int K
                           const float *R, long strideR, float *Y, long strideY,
                           const float *W1, const float *b1, float *Z, long strideZ,
                           int Co, int C1, int HW, int batch, int act_z, void *stream);
+
+int dfx_gemm_wgrad_f32(const float *dY, long ldy, const float *X, long ldx,
+                       float *dW, long ldw, float *db,
+                       int M, int N, int K, int splits, float *workspace, void *stream);
 
 #ifdef __cplusplus
 }
