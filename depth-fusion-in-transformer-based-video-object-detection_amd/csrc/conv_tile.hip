@@ -271,26 +271,10 @@ extern "C" int dfx_conv2d_tile_f32(const float *x, const float *wp, const float 
     const size_t lds = (size_t)(32 * MT * (Kpad + 4) + Kpad + 2 * Ci * g.IH * g.PW + 32 * MT) * 4;
     if (lds > 160 * 1024) return dfx::fail(DFX_EINVAL, "conv2d_tile: the staged tile does not fit the LDS");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    static std::mutex mu;
-    static bool raised_on[64] = {false};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    {
-        std::lock_guard<std::mutex> lock(mu);
-        if (!raised_on[dev & 63]) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_tile_kernel<1, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-                hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_tile_kernel<1, kMaxStage>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-                hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_tile_kernel<2, kMaxStage>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-                return dfx::fail(DFX_ELAUNCH, "conv2d_tile: cannot raise the dynamic LDS limit");
-            raised_on[dev & 63] = true;
-        }
-    }
-    static int ncu = 0;
-    if (ncu == 0) {
-        int n = 0;
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 8) n = 256;
-        ncu = n;
-    }
+    if (const int rc = dfx::raise_lds_limit<&conv_tile_kernel<1, 3>, &conv_tile_kernel<1, kMaxStage>, &conv_tile_kernel<2, kMaxStage>>(
+            "conv2d_tile", 160 * 1024))
+        return rc;
+    static const int ncu = dfx::cu_count();
     // workgroups per CU: what the LDS allows, at most 4 (2048 threads); the one-K-step convolutions (K <= 16) are bound by the
     // latency of a tile's loads and stores, not by the matrix pipe: they want all four
     const long per_cu = lds * 4 <= 160 * 1024 ? 4 : lds * 2 <= 160 * 1024 ? 2 : 1;

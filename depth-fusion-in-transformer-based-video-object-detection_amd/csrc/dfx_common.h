@@ -148,6 +148,44 @@ inline int check_dims(const void *value, const void *shapes, const void *lsi, co
 
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// ---- launch plumbing shared by the kernels with a large LDS image --------------------------
+// A launch with more than 64 KB of dynamic LDS needs hipFuncAttributeMaxDynamicSharedMemorySize raised on every
+// kernel it may pick, once per DEVICE (the attribute belongs to the device's code object).  The flags are one
+// per (kernel list, device) - the kernel list is the call site - under one mutex; a device that cannot be
+// identified or lies outside the table is an error, never another device's flag.
+constexpr int kMaxDevices = 64;
+
+inline std::mutex &lds_limit_mutex()
+{
+    static std::mutex mu;
+    return mu;
+}
+
+template <auto... Kernels>
+inline int raise_lds_limit(const char *what, int bytes)
+{
+    static bool raised_on[kMaxDevices] = {};
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices)
+        return fail(DFX_ELAUNCH, "%s: cannot identify the current device", what);
+    std::lock_guard<std::mutex> lock(lds_limit_mutex());
+    if (raised_on[dev]) return DFX_OK;
+    for (const void *fn : {reinterpret_cast<const void *>(Kernels)...})
+        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess)
+            return fail(DFX_ELAUNCH, "%s: cannot raise the dynamic LDS limit", what);
+    raised_on[dev] = true;
+    return DFX_OK;
+}
+
+// CUs of the current device; 256 (an MI355X) when the count cannot be read or is below 8.  Callers that size a
+// persistent grid keep the first answer in a function-local static.
+inline int cu_count()
+{
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 8) n = 256;
+    return n;
+}
+
 inline int grid_for(long total, int block = 256, int cap = 16384)
 {
     const long g = (total + block - 1) / block;

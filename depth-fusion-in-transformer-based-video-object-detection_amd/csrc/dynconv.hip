@@ -234,15 +234,7 @@ extern "C" int dfx_dynamic_conv_f32(const float *feats, const float *params, lon
         !dfx::aligned16(out) || !dfx::aligned16(g1) || !dfx::aligned16(b1) || !dfx::aligned16(g2) || !dfx::aligned16(b2))
         return dfx::fail(DFX_EINVAL, "dynamic_conv: params rows must hold 2*C*dd floats, 16-byte aligned buffers");
     const size_t lds = sizeof(float) * (RP * XP + C * DD + RP * YP + 2 * DD + 2 * C);
-    static bool raised = false;
-    if (!raised) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(&dynamic_conv<X_F4>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void *>(&dynamic_conv<X_F4_MAX>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-            return dfx::fail(DFX_ELAUNCH, "dynamic_conv: cannot raise the dynamic LDS limit");
-        raised = true;
-    }
+    if (const int rc = dfx::raise_lds_limit<&dynamic_conv<X_F4>, &dynamic_conv<X_F4_MAX>>("dynamic_conv", 160 * 1024)) return rc;
     const int grid = K < 256 ? K : 256;         // one persistent workgroup per CU
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (R <= 49)

@@ -493,19 +493,9 @@ extern "C" int dfx_dynamic_conv_backward_f32(const float *grad_out, const float 
         (grad_params && (gp_stride < 2L * C * DD || (gp_stride & 3))))
         return dfx::fail(DFX_EINVAL, "dynamic_conv_backward: params / grad_params rows must hold 2*C*dd floats, 16-byte aligned buffers");
     const size_t lds = sizeof(float) * (RP * XP + C * DD + RP * YP + LN_FLOATS + 2 * RP);
-    static bool raised_on[64] = {};             // the attribute is per device
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64)
-        return dfx::fail(DFX_ELAUNCH, "dynamic_conv_backward: cannot identify the current device");
-    bool &raised = raised_on[dev];
-    if (!raised) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(&dynamic_conv_backward<X_F4>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void *>(&dynamic_conv_backward<X_F4_MAX>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-            return dfx::fail(DFX_ELAUNCH, "dynamic_conv_backward: cannot raise the dynamic LDS limit");
-        raised = true;
-    }
+    if (const int rc = dfx::raise_lds_limit<&dynamic_conv_backward<X_F4>, &dynamic_conv_backward<X_F4_MAX>>(
+            "dynamic_conv_backward", 160 * 1024))
+        return rc;
     const int grid = K < 256 ? K : 256;         // one persistent workgroup per CU; fixed for a given K: reproducible sums
     if (R <= 49)
         hipLaunchKernelGGL(dynamic_conv_backward<X_F4>, dim3(grid), dim3(256), lds, st, grad_out, feats, params, p_stride, g1,

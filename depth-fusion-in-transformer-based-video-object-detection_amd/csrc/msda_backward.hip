@@ -7,7 +7,7 @@
 //
 // Here the production geometry (M=8, D=32, fp32) keeps the forward's mapping - one wave per query,
 // lane = (head, channel quad) - so the 32 channels of a head live in 8 adjacent lanes x 4 registers
-// and the reduction is 3 in-register adds + 3 DPP/xor shuffles; no LDS, no barrier.  grad_value is
+// and the reduction is 3 in-register adds + 3 DPP/xor shuffles (head_sum, msda_tap.h); no LDS, no barrier.  grad_value is
 // scattered with hardware float atomics (global_atomic_add_f32: 4 per corner per lane, 128
 // contiguous bytes per head row).  Every other geometry (and fp64) takes a thread-per-element
 // path that accumulates all three gradients with atomics, like the reference's `_gm` variant
@@ -25,16 +25,8 @@
 namespace {
 
 using dfx::Acc;
+using dfx::head_sum;
 using dfx::xcd_remap;
-
-__device__ __forceinline__ float head_sum(float v)
-{
-    // sum over the 8 lanes (lane&7) that share one head
-    v += __shfl_xor(v, 1, 64);
-    v += __shfl_xor(v, 2, 64);
-    v += __shfl_xor(v, 4, 64);
-    return v;
-}
 
 // 4 consecutive channels as fp32: one 16-byte load, or one 8-byte load of 2-byte channels widened
 template <typename V>

@@ -301,14 +301,11 @@ int forward_impl(const V *value, const int64_t *shapes, const int64_t *lsi, cons
         const bool fast = M == 8 && D == 32 && nq < (1L << 28) && (long)S * 1024 < (1L << 32) &&
                           dfx::aligned16(value) && dfx::aligned16(out);
         if (fast && P == 4 && L <= 4 && (reinterpret_cast<uintptr_t>(loc) & 7u) == 0) {
-            // 8 queries per workgroup and iteration; keep >= ~2048 workgroups in the grid when we can
-            int iters = 1;
-            while (iters < 8 && nq / (8L * iters * 2) >= 2048) iters *= 2;
-            const int grid = (int)((nq + 8L * iters - 1) / (8L * iters));
+            const dfx::TapsGrid tg = dfx::taps_grid(nq);
             const bool wide = half && L == 1 && !dfx::tuning().msda_half_narrow;
 #define DFX_TAPS(LT, WIDE)                                                                                  \
-            hipLaunchKernelGGL((msda_fwd_taps<LT, V, WIDE>), dim3(grid), dim3(256), 0, st, value, shapes, lsi, loc, \
-                               aw, (int)nq, Lq, S, iters, out)
+            hipLaunchKernelGGL((msda_fwd_taps<LT, V, WIDE>), dim3(tg.blocks), dim3(256), 0, st, value, shapes, lsi, \
+                               loc, aw, (int)nq, Lq, S, tg.iters, out)
             if constexpr (half) {   // the wide gather is built for 2-byte values at L = 1 only
                 if (wide) DFX_TAPS(1, true);
             }

@@ -8,7 +8,8 @@
 // directly, in the two-phase structure of msda_forward.hip: in phase A each lane owns one
 // (query, level, point, head) sample, computes its softmax weight (the L*P logits of its head are
 // one or a few 16-byte loads; <= 16 exponentials) and its location, and stages the resulting tap
-// in LDS; phase B is the shared 16-byte corner gather (msda_tap.h).
+// in LDS; phase B is the shared 16-byte corner gather.  The slot decode and the location rule are routines
+// of msda_tap.h; the backward (msda_fused_backward.hip) calls the same location rule.
 //
 // `Lr` is the number of reference-point levels.  Lr == L is the normal module.  Lr > L (with
 // L == 1) is the TransVOD temporal decoder: the module there builds a location tensor
@@ -49,7 +50,7 @@ __global__ __launch_bounds__(256) void msda_fused_taps(const float *__restrict__
     const int m = lane >> 3;
     const unsigned lane_b = (unsigned)(lane & 7) * 16u;
 
-    int Hs[LT], Ws[LT], Rs[LT];
+    int Hs[LT], Ws[LT], Rs[LT];      // level sizes and their select stay in this kernel: on a shared routine <2, 2> takes 116 VGPRs (96 here)
 #pragma unroll
     for (int l = 0; l < LT; ++l) {
         Hs[l] = (int)shapes[2 * l];
@@ -63,12 +64,13 @@ __global__ __launch_bounds__(256) void msda_fused_taps(const float *__restrict__
 #pragma unroll
         for (int c = 0; c < TAPS / 64; ++c) {
             const int s = c * 64 + lane;                 // slot = ((qq*LT + l)*4 + p)*8 + head
-            const int hm = s & 7, p = (s >> 3) & 3, ql = s >> 5;
-            const int l = (LT == 1) ? 0 : ql % LT, qq = (LT == 1) ? ql : ql / LT;
-            const int qi = q0 + qq;
+            const dfx::Slot<LT> sl(s);
+            const int hm = sl.hm, p = sl.p, l = sl.l, qi = q0 + sl.qq;
             Tap t;
             if (qi < NQ) {
-                // ---- attention weight: softmax over the L*P logits of (query, head), F.softmax(x,-1)
+                // ---- attention weight: softmax over the L*P logits of (query, head), F.softmax(x,-1).  msda_fused_bwd
+                //      restates these lines (max over the float4s, expf(x - max), sum in index order): as a routine of
+                //      msda_tap.h they cost <4, 4> a wave per SIMD
                 const float *lg = logits + (long)qi * logit_stride + hm * (LT * 4);
                 float4 e[LT];
                 float mx = -INFINITY;
@@ -106,17 +108,8 @@ __global__ __launch_bounds__(256) void msda_fused_taps(const float *__restrict__
 #pragma unroll
                 for (int k = 1; k < LT; ++k)
                     if (l == k) { H = Hs[k]; W = Ws[k]; R = Rs[k]; }
-                float x, y;
-                if (REFDIM == 2) {
-                    // ref + off / (W_lo, H_lo)   (ms_deform_attn.py:102-107); lo == l unless Lr != L (then L == 1)
-                    x = rp[0] + o2.x / (float)W;
-                    y = rp[1] + o2.y / (float)H;
-                } else {
-                    // ref_xy + off / P * ref_wh * 0.5   (ms_deform_attn.py:108-110)
-                    const float4 rr = *reinterpret_cast<const float4 *>(rp);
-                    x = rr.x + o2.x / 4.f * rr.z * 0.5f;
-                    y = rr.y + o2.y / 4.f * rr.w * 0.5f;
-                }
+                const float2 xy = dfx::sample_location<REFDIM>(dfx::load_ref<REFDIM>(rp), o2.x, o2.y, W, H);
+                const float x = xy.x, y = xy.y;
                 t = dfx::make_tap(x, y, a, H, W, R, hm * 128);
             } else {
                 t.off = make_uint4(0u, 0u, 0u, 0u);
@@ -140,22 +133,15 @@ __global__ __launch_bounds__(256) void msda_fused_taps(const float *__restrict__
     }
 }
 
-template <int LT>
-int launch(int ref_dim, const float *value, const int64_t *shapes, const int64_t *lsi, const float *ref,
-           int Lr, const float *off, long off_stride, const float *logits, long logit_stride, int NQ,
-           int Lq, int S, float *out, hipStream_t st)
+template <int LT, int REFDIM>
+int launch(const float *value, const int64_t *shapes, const int64_t *lsi, const float *ref, int Lr, const float *off,
+           long off_stride, const float *logits, long logit_stride, int NQ, int Lq, int S, float *out, hipStream_t st)
 {
-    int iters = 1;
-    while (iters < 8 && NQ / (8L * iters * 2) >= 2048) iters *= 2;
-    const dim3 grid((unsigned)((NQ + 8L * iters - 1) / (8L * iters))), block(256);
+    const dfx::TapsGrid tg = dfx::taps_grid(NQ);
     // algorithmic bytes of this launch: value + (offsets, logits) + out, fp32
     const long bytes = 4L * ((long)(NQ / Lq) * S * 256 + 3L * NQ * 8 * LT * 4 + (long)NQ * 256);
-    if (ref_dim == 2)
-        dfx::launch_timed(bytes, Lq, S, msda_fused_taps<LT, 2>, grid, block, 0, st, value, shapes, lsi, ref, Lr, off,
-                          off_stride, logits, logit_stride, NQ, Lq, S, iters, out);
-    else
-        dfx::launch_timed(bytes, Lq, S, msda_fused_taps<LT, 4>, grid, block, 0, st, value, shapes, lsi, ref, Lr, off,
-                          off_stride, logits, logit_stride, NQ, Lq, S, iters, out);
+    dfx::launch_timed(bytes, Lq, S, msda_fused_taps<LT, REFDIM>, dim3(tg.blocks), dim3(256), 0, st, value, shapes, lsi, ref, Lr,
+                      off, off_stride, logits, logit_stride, NQ, Lq, S, tg.iters, out);
     return dfx::check_launch("msda_fused_taps");
 }
 
@@ -167,33 +153,21 @@ extern "C" int dfx_msda_fused_forward_f32(const float *value, const int64_t *sha
                                           int S, int M, int D, int L, int Lq, int P, float *out,
                                           void *stream)
 {
-    const int rc = dfx::check_dims(value, shapes, lsi, off, logits, out, N, S, M, D, L, Lq, P);
+    const int rc = dfx::check_fused("msda fused", "dfx_msda_forward_f32", value, shapes, lsi, ref, ref_dim, off, off_stride,
+                                    logits, logit_stride, out, N, S, M, D, L, Lq, P);
     if (rc < 0) return rc;
     if (rc == 1) return DFX_OK;
-    if (!ref) return dfx::fail(DFX_EINVAL, "msda fused: null reference points");
-    if (ref_dim != 2 && ref_dim != 4) return dfx::fail(DFX_EINVAL, "msda fused: ref_dim must be 2 or 4, got %d", ref_dim);
-    if (M != 8 || D != 32 || P != 4 || L < 1 || L > 4)
-        return dfx::fail(DFX_EINVAL, "msda fused: only M=8, D=32, P=4, 1<=L<=4 is fused (got M=%d D=%d P=%d L=%d); "
-                                     "use dfx_msda_forward_f32", M, D, P, L);
     if (Lr != L && !(L == 1 && Lr >= 1))
         return dfx::fail(DFX_EINVAL, "msda fused: Lr (%d) must equal L (%d) unless L == 1", Lr, L);
-    if (off_stride < (long)M * L * P * 2 || logit_stride < (long)M * L * P || (off_stride & 3) || (logit_stride & 3))
-        return dfx::fail(DFX_EINVAL, "msda fused: bad row strides");
-    if (!dfx::aligned16(value) || !dfx::aligned16(out) || !dfx::aligned16(off) || !dfx::aligned16(logits) ||
-        (ref_dim == 4 && !dfx::aligned16(ref)))
-        return dfx::fail(DFX_EINVAL, "msda fused: buffers must be 16-byte aligned");
     const long nq = (long)N * Lq;
-    if (nq >= (1L << 28) || (long)S * 1024 >= (1L << 32)) return dfx::fail(DFX_ERANGE, "msda fused: problem too large");
+    hipStream_t st = static_cast<hipStream_t>(stream);
     if (S == 0) {
-        if (hipMemsetAsync(out, 0, sizeof(float) * nq * M * D, static_cast<hipStream_t>(stream)) != hipSuccess)
+        if (hipMemsetAsync(out, 0, sizeof(float) * nq * M * D, st) != hipSuccess)
             return dfx::fail(DFX_ELAUNCH, "msda fused: memset failed");
         return DFX_OK;
     }
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    switch (L) {
-        case 1: return launch<1>(ref_dim, value, shapes, lsi, ref, Lr, off, off_stride, logits, logit_stride, (int)nq, Lq, S, out, st);
-        case 2: return launch<2>(ref_dim, value, shapes, lsi, ref, Lr, off, off_stride, logits, logit_stride, (int)nq, Lq, S, out, st);
-        case 3: return launch<3>(ref_dim, value, shapes, lsi, ref, Lr, off, off_stride, logits, logit_stride, (int)nq, Lq, S, out, st);
-        default: return launch<4>(ref_dim, value, shapes, lsi, ref, Lr, off, off_stride, logits, logit_stride, (int)nq, Lq, S, out, st);
-    }
+    return dfx::dispatch_fused(L, ref_dim, [&](auto lt, auto rd) {
+        return launch<decltype(lt)::value, decltype(rd)::value>(value, shapes, lsi, ref, Lr, off, off_stride, logits, logit_stride,
+                                                                (int)nq, Lq, S, out, st);
+    });
 }

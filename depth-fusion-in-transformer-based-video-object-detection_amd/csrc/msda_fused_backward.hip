@@ -2,11 +2,15 @@
 //
 // The backward of dfx_msda_fused_forward_f32 (msda_fused.hip) from the forward's own raw inputs: the two
 // Linear outputs (offsets, logits), the reference points and the value map.  Nothing else is saved by the
-// caller: the kernel recomputes the softmax weights and the sampling locations with the forward's
-// arithmetic, so sampling_locations / attention_weights never exist in HBM in either direction.
+// caller: the kernel recomputes the softmax weights with the forward's arithmetic and the sampling locations by
+// calling the forward's routines (msda_tap.h: load_ref, sample_location), so sampling_locations /
+// attention_weights never exist in HBM in either direction.
 //
 // Mapping: msda_bwd_m8d32's (msda_backward.hip) - one wave per query, lane = (head, channel quad), the 32
 // channels of a head in 8 adjacent lanes x 4 registers, reductions over them by 3 xor shuffles (head_sum).
+// The gradient of one sample (corner<> and the block around it) is kept in this file, next to msda_bwd_m8d32's:
+// moved into a routine both kernels call, hipcc packs and contracts its products differently and grad_off,
+// grad_logits, grad_ref and grad_loc change in the last bit.
 // The 4*LT softmax weights of the lane's head and the 4*LT gradients g_a with respect to them stay in
 // registers (LT levels and P = 4 points are compile-time), which is all the softmax backward needs:
 //     grad_logits[k] = a[k] * (g_a[k] - sum_j a[j] * g_a[j]).
@@ -25,28 +29,13 @@
 // caller passes none (the memory is detached) the NEED_VALUE = false instantiation contains no atomic and no
 // corner store at all.
 #include "dfx_common.h"
+#include "msda_tap.h"
 
 namespace {
 
+using dfx::all_heads_sum;
+using dfx::head_sum;
 using dfx::xcd_remap;
-
-__device__ __forceinline__ float head_sum(float v)
-{
-    // sum over the 8 lanes (lane&7) that share one head
-    v += __shfl_xor(v, 1, 64);
-    v += __shfl_xor(v, 2, 64);
-    v += __shfl_xor(v, 4, 64);
-    return v;
-}
-
-__device__ __forceinline__ float all_heads_sum(float v)
-{
-    // v is uniform over the 8 lanes of a head: sum over the 8 heads of the wave
-    v += __shfl_xor(v, 8, 64);
-    v += __shfl_xor(v, 16, 64);
-    v += __shfl_xor(v, 32, 64);
-    return v;
-}
 
 // One bilinear corner: its share of d out / d (h, w, weight) and, with NEED_VALUE, of grad_value.
 template <bool NEED_VALUE>
@@ -65,32 +54,42 @@ __device__ __forceinline__ void corner(const float *__restrict__ vl, float *__re
     }
 }
 
+// Filled by name in the entry point, passed by value.
+struct FusedBwdArgs {
+    const float *value;
+    const int64_t *shapes, *lsi;
+    const float *ref, *off, *logits, *grad_out;
+    float *grad_value, *grad_off, *grad_logits, *grad_ref;      // grad_value, grad_ref: may be null
+    long off_stride, logit_stride, goff_stride, glog_stride;
+    int NQ, Lq, S;
+};
+
 template <int LT, int REFDIM, bool NEED_VALUE>
-__global__ __launch_bounds__(256) void msda_fused_bwd(const float *__restrict__ value,
-                                                      const int64_t *__restrict__ shapes,
-                                                      const int64_t *__restrict__ lsi,
-                                                      const float *__restrict__ ref,
-                                                      const float *__restrict__ off, long off_stride,
-                                                      const float *__restrict__ logits, long logit_stride,
-                                                      const float *__restrict__ grad_out, int NQ, int Lq, int S,
-                                                      float *__restrict__ grad_value,
-                                                      float *__restrict__ grad_off, long goff_stride,
-                                                      float *__restrict__ grad_logits, long glog_stride,
-                                                      float *__restrict__ grad_ref)
+__global__ __launch_bounds__(256) void msda_fused_bwd(const FusedBwdArgs g)
 {
     const int blk = xcd_remap(blockIdx.x, gridDim.x);
     const int lane = threadIdx.x & 63;
     const int qi = blk * 4 + (threadIdx.x >> 6);
-    if (qi >= NQ) return;                       // whole wave leaves together: shuffles below are safe
+    if (qi >= g.NQ) return;                     // whole wave leaves together: shuffles below are safe
     const int m = lane >> 3, cg = lane & 7;
-    const int b = qi / Lq;
-    const long chan = (long)b * S * 256 + m * 32 + cg * 4;
-    const float4 top = *reinterpret_cast<const float4 *>(grad_out + (long)qi * 256 + lane * 4);
+    const int b = qi / g.Lq;
+    const long chan = (long)b * g.S * 256 + m * 32 + cg * 4;
+    const float4 top = *reinterpret_cast<const float4 *>(g.grad_out + (long)qi * 256 + lane * 4);
 
-    // ---- softmax over the head's L*P logits, the forward's arithmetic (msda_fused.hip)
+    // every level's size up front, as the taps kernels do: read per level between the stores and atomics of the loop
+    // below they cost two VGPRs (the struct's pointers carry no __restrict__) and, at L = 2, a wave per SIMD
+    dfx::LevelDims<LT> lv;
+#pragma unroll
+    for (int l = 0; l < LT; ++l) {
+        lv.H[l] = (int)g.shapes[2 * l];
+        lv.W[l] = (int)g.shapes[2 * l + 1];
+        lv.R[l] = (int)g.lsi[l];
+    }
+
+    // ---- softmax over the head's L*P logits: the forward's arithmetic restated (msda_fused.hip says why), keep the two alike
     float a[LT * 4], ga[LT * 4];
     {
-        const float *lg = logits + (long)qi * logit_stride + m * (LT * 4);
+        const float *lg = g.logits + (long)qi * g.logit_stride + m * (LT * 4);
         float mx = -INFINITY;
 #pragma unroll
         for (int k = 0; k < LT; ++k) {
@@ -110,37 +109,22 @@ __global__ __launch_bounds__(256) void msda_fused_bwd(const float *__restrict__ 
 
 #pragma unroll
     for (int l = 0; l < LT; ++l) {
-        const int H = (int)shapes[2 * l], W = (int)shapes[2 * l + 1];
-        const long lvl = chan + (long)((int)lsi[l]) * 256;
-        const float *vl = value + lvl;
-        float *gl = NEED_VALUE ? grad_value + lvl : nullptr;
-        const float *rp = ref + ((long)qi * LT + l) * REFDIM;
-        float rx, ry, kx = 0.f, ky = 0.f;       // location = r + offset * k (ref_dim 4) or r + offset / size (ref_dim 2)
-        if (REFDIM == 2) {
-            rx = rp[0];
-            ry = rp[1];
-        } else {
-            const float4 rr = *reinterpret_cast<const float4 *>(rp);
-            rx = rr.x; ry = rr.y; kx = rr.z; ky = rr.w;
-        }
-        const float4 *op = reinterpret_cast<const float4 *>(off + (long)qi * off_stride + (m * LT + l) * 8);
+        const int H = lv.H[l], W = lv.W[l];
+        const long lvl = chan + (long)lv.R[l] * 256;
+        const float *vl = g.value + lvl;
+        float *gl = NEED_VALUE ? g.grad_value + lvl : nullptr;
+        const dfx::RefPoint r = dfx::load_ref<REFDIM>(g.ref + ((long)qi * LT + l) * REFDIM);
+        const float4 *op = reinterpret_cast<const float4 *>(g.off + (long)qi * g.off_stride + (m * LT + l) * 8);
         const float4 o01 = op[0], o23 = op[1];
         const float ox[4] = {o01.x, o01.z, o23.x, o23.z}, oy[4] = {o01.y, o01.w, o23.y, o23.w};
         float gox[4], goy[4];
         float rgx = 0.f, rgy = 0.f, rgw = 0.f, rgh = 0.f;
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
-            float x, y;
-            if (REFDIM == 2) {
-                x = rx + ox[p] / (float)W;
-                y = ry + oy[p] / (float)H;
-            } else {
-                x = rx + ox[p] / 4.f * kx * 0.5f;
-                y = ry + oy[p] / 4.f * ky * 0.5f;
-            }
+            const float2 xy = dfx::sample_location<REFDIM>(r, ox[p], oy[p], W, H);
+            const float h_im = xy.y * (float)H - 0.5f;
+            const float w_im = xy.x * (float)W - 0.5f;
             const float weight = a[l * 4 + p];
-            const float h_im = y * (float)H - 0.5f;
-            const float w_im = x * (float)W - 0.5f;
             float s_w = 0.f, s_h = 0.f, g_a = 0.f;
             // the in-range test depends on (query, head) only: uniform over the 8 lanes of a head
             if (h_im > -1.f && w_im > -1.f && h_im < (float)H && w_im < (float)W) {
@@ -165,8 +149,8 @@ __global__ __launch_bounds__(256) void msda_fused_bwd(const float *__restrict__ 
                 gox[p] = s_w;
                 goy[p] = s_h;
             } else {
-                gox[p] = g_x * kx * 0.5f / 4.f;
-                goy[p] = g_y * ky * 0.5f / 4.f;
+                gox[p] = g_x * r.kx * 0.5f / 4.f;
+                goy[p] = g_y * r.ky * 0.5f / 4.f;
                 rgw += g_x * ox[p];
                 rgh += g_y * oy[p];
             }
@@ -174,14 +158,14 @@ __global__ __launch_bounds__(256) void msda_fused_bwd(const float *__restrict__ 
             rgy += g_y;
         }
         if (cg == l) {      // the 8 lanes of a head hold the same sums: lane l of the head stores level l
-            float4 *gp = reinterpret_cast<float4 *>(grad_off + (long)qi * goff_stride + (m * LT + l) * 8);
+            float4 *gp = reinterpret_cast<float4 *>(g.grad_off + (long)qi * g.goff_stride + (m * LT + l) * 8);
             gp[0] = make_float4(gox[0], goy[0], gox[1], goy[1]);
             gp[1] = make_float4(gox[2], goy[2], gox[3], goy[3]);
         }
-        if (grad_ref) {     // wave-uniform
+        if (g.grad_ref) {   // wave-uniform
             rgx = all_heads_sum(rgx);
             rgy = all_heads_sum(rgy);
-            float *gr = grad_ref + ((long)qi * LT + l) * REFDIM;
+            float *gr = g.grad_ref + ((long)qi * LT + l) * REFDIM;
             if (REFDIM == 2) {
                 if (lane == l) *reinterpret_cast<float2 *>(gr) = make_float2(rgx, rgy);
             } else {
@@ -196,7 +180,7 @@ __global__ __launch_bounds__(256) void msda_fused_bwd(const float *__restrict__ 
     float dot = 0.f;
 #pragma unroll
     for (int k = 0; k < LT * 4; ++k) dot += a[k] * ga[k];
-    float *gq = grad_logits + (long)qi * glog_stride + m * (LT * 4);
+    float *gq = g.grad_logits + (long)qi * g.glog_stride + m * (LT * 4);
 #pragma unroll
     for (int k = 0; k < LT; ++k)
         if (cg == k)
@@ -205,28 +189,11 @@ __global__ __launch_bounds__(256) void msda_fused_bwd(const float *__restrict__ 
                             a[k * 4 + 2] * (ga[k * 4 + 2] - dot), a[k * 4 + 3] * (ga[k * 4 + 3] - dot));
 }
 
-template <int LT, int REFDIM>
-int launch_ref(const float *value, const int64_t *shapes, const int64_t *lsi, const float *ref, const float *off,
-               long off_stride, const float *logits, long logit_stride, const float *grad_out, int NQ, int Lq, int S,
-               float *grad_value, float *grad_off, long goff_stride, float *grad_logits, long glog_stride,
-               float *grad_ref, hipStream_t st)
+template <int LT, int REFDIM, bool NEED_VALUE>
+int launch(const FusedBwdArgs &g, hipStream_t st)
 {
-    const dim3 grid((unsigned)((NQ + 3) / 4)), block(256);
-    if (grad_value)
-        hipLaunchKernelGGL((msda_fused_bwd<LT, REFDIM, true>), grid, block, 0, st, value, shapes, lsi, ref, off, off_stride,
-                           logits, logit_stride, grad_out, NQ, Lq, S, grad_value, grad_off, goff_stride, grad_logits,
-                           glog_stride, grad_ref);
-    else
-        hipLaunchKernelGGL((msda_fused_bwd<LT, REFDIM, false>), grid, block, 0, st, value, shapes, lsi, ref, off, off_stride,
-                           logits, logit_stride, grad_out, NQ, Lq, S, grad_value, grad_off, goff_stride, grad_logits,
-                           glog_stride, grad_ref);
+    hipLaunchKernelGGL((msda_fused_bwd<LT, REFDIM, NEED_VALUE>), dim3((unsigned)((g.NQ + 3) / 4)), dim3(256), 0, st, g);
     return dfx::check_launch("msda_fused_bwd");
-}
-
-template <int LT, typename... Args>
-int launch(int ref_dim, Args... args)
-{
-    return ref_dim == 2 ? launch_ref<LT, 2>(args...) : launch_ref<LT, 4>(args...);
 }
 
 }  // namespace
@@ -238,39 +205,33 @@ extern "C" int dfx_msda_fused_backward_f32(const float *value, const int64_t *sh
                                            float *grad_off, long grad_off_stride, float *grad_logits,
                                            long grad_logit_stride, float *grad_ref, void *stream)
 {
-    const int rc = dfx::check_dims(value, shapes, lsi, off, logits, grad_out, N, S, M, D, L, Lq, P);
+    const char *what = "msda fused backward";
+    const int rc = dfx::check_fused(what, "dfx_msda_backward_f32", value, shapes, lsi, ref, ref_dim, off, off_stride, logits,
+                                    logit_stride, grad_out, N, S, M, D, L, Lq, P);
     if (rc < 0) return rc;
     if (rc == 1) return DFX_OK;
-    if (!ref) return dfx::fail(DFX_EINVAL, "msda fused backward: null reference points");
-    if (!grad_off || !grad_logits) return dfx::fail(DFX_EINVAL, "msda fused backward: null gradient buffer");
-    if (ref_dim != 2 && ref_dim != 4)
-        return dfx::fail(DFX_EINVAL, "msda fused backward: ref_dim must be 2 or 4, got %d", ref_dim);
-    if (M != 8 || D != 32 || P != 4 || L < 1 || L > 4)
-        return dfx::fail(DFX_EINVAL, "msda fused: only M=8, D=32, P=4, 1<=L<=4 is fused (got M=%d D=%d P=%d L=%d); "
-                                     "use dfx_msda_backward_f32", M, D, P, L);
+    if (!grad_off || !grad_logits) return dfx::fail(DFX_EINVAL, "%s: null gradient buffer", what);
     const long orow = (long)M * L * P * 2, lrow = (long)M * L * P;
-    if (off_stride < orow || logit_stride < lrow || grad_off_stride < orow || grad_logit_stride < lrow ||
-        ((off_stride | logit_stride | grad_off_stride | grad_logit_stride) & 3))
-        return dfx::fail(DFX_EINVAL, "msda fused backward: bad row strides");
-    if (!dfx::aligned16(value) || !dfx::aligned16(grad_out) || !dfx::aligned16(off) || !dfx::aligned16(logits) ||
-        !dfx::aligned16(grad_value) || !dfx::aligned16(grad_off) || !dfx::aligned16(grad_logits) ||
-        !dfx::aligned16(grad_ref) || (ref_dim == 4 && !dfx::aligned16(ref)))
-        return dfx::fail(DFX_EINVAL, "msda fused backward: buffers must be 16-byte aligned");
+    if (grad_off_stride < orow || grad_logit_stride < lrow || ((grad_off_stride | grad_logit_stride) & 3))
+        return dfx::fail(DFX_EINVAL, "%s: bad row strides", what);
+    if (!dfx::aligned16(grad_value) || !dfx::aligned16(grad_off) || !dfx::aligned16(grad_logits) || !dfx::aligned16(grad_ref))
+        return dfx::fail(DFX_EINVAL, "%s: buffers must be 16-byte aligned", what);
     const long nq = (long)N * Lq;
-    if (nq >= (1L << 28) || (long)S * 1024 >= (1L << 32))
-        return dfx::fail(DFX_ERANGE, "msda fused backward: problem too large");
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (S == 0) {
         if (hipMemset2DAsync(grad_off, sizeof(float) * grad_off_stride, 0, sizeof(float) * orow, nq, st) != hipSuccess ||
             hipMemset2DAsync(grad_logits, sizeof(float) * grad_logit_stride, 0, sizeof(float) * lrow, nq, st) != hipSuccess ||
             (grad_ref && hipMemsetAsync(grad_ref, 0, sizeof(float) * nq * L * ref_dim, st) != hipSuccess))
-            return dfx::fail(DFX_ELAUNCH, "msda fused backward: memset failed");
+            return dfx::fail(DFX_ELAUNCH, "%s: memset failed", what);
         return DFX_OK;
     }
-    switch (L) {
-        case 1: return launch<1>(ref_dim, value, shapes, lsi, ref, off, off_stride, logits, logit_stride, grad_out, (int)nq, Lq, S, grad_value, grad_off, grad_off_stride, grad_logits, grad_logit_stride, grad_ref, st);
-        case 2: return launch<2>(ref_dim, value, shapes, lsi, ref, off, off_stride, logits, logit_stride, grad_out, (int)nq, Lq, S, grad_value, grad_off, grad_off_stride, grad_logits, grad_logit_stride, grad_ref, st);
-        case 3: return launch<3>(ref_dim, value, shapes, lsi, ref, off, off_stride, logits, logit_stride, grad_out, (int)nq, Lq, S, grad_value, grad_off, grad_off_stride, grad_logits, grad_logit_stride, grad_ref, st);
-        default: return launch<4>(ref_dim, value, shapes, lsi, ref, off, off_stride, logits, logit_stride, grad_out, (int)nq, Lq, S, grad_value, grad_off, grad_off_stride, grad_logits, grad_logit_stride, grad_ref, st);
-    }
+    FusedBwdArgs g{};
+    g.value = value; g.shapes = shapes; g.lsi = lsi; g.ref = ref; g.off = off; g.logits = logits; g.grad_out = grad_out;
+    g.grad_value = grad_value; g.grad_off = grad_off; g.grad_logits = grad_logits; g.grad_ref = grad_ref;
+    g.off_stride = off_stride; g.logit_stride = logit_stride; g.goff_stride = grad_off_stride; g.glog_stride = grad_logit_stride;
+    g.NQ = (int)nq; g.Lq = Lq; g.S = S;
+    return dfx::dispatch_fused(L, ref_dim, [&](auto lt, auto rd) {
+        constexpr int LT = decltype(lt)::value, RD = decltype(rd)::value;
+        return grad_value ? launch<LT, RD, true>(g, st) : launch<LT, RD, false>(g, st);
+    });
 }

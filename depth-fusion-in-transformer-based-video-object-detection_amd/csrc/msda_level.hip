@@ -221,20 +221,7 @@ extern "C" int dfx_msda_fused_level_forward_f32(const float *value, const float 
     const int PL = (int)plane_tokens(H, W);
     const size_t lds = (size_t)2 * PL * 16;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    // LDS images above 64 KB need the per-function opt-in, once per DEVICE (the attribute is per device context)
-    static std::mutex raise_mu;
-    static bool raised_on[64] = {false};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    std::lock_guard<std::mutex> raise_lock(raise_mu);
-    bool &raised = raised_on[dev & 63];
-    if (!raised) {
-        const void *fns[2] = {reinterpret_cast<const void *>(&msda_fused_level<2>), reinterpret_cast<const void *>(&msda_fused_level<4>)};
-        for (const void *fn : fns)
-            if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_CAP) != hipSuccess)
-                return dfx::fail(DFX_ELAUNCH, "msda level: cannot raise the dynamic LDS limit");
-        raised = true;
-    }
+    if (const int rc = dfx::raise_lds_limit<&msda_fused_level<2>, &msda_fused_level<4>>("msda level", (int)LDS_CAP)) return rc;
     const int S = H * W;
     const LevelArgs g{value, ref, off, logits, out, ly, H, W, Lq, PL, qsplit, (int)blocks};
     // persistent: at most one workgroup per CU, a multiple of 8 so that item & 7 (the head) is fixed per workgroup

@@ -152,23 +152,9 @@ extern "C" int dfx_msda_level_grad_value_f32(const float *ref, int ref_dim, cons
     const int PL = (int)plane_tokens(H, W);
     const size_t lds = (size_t)2 * PL * 16;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    // LDS images above 64 KB need the per-function opt-in, once per DEVICE (the attribute is per device context)
-    {
-        static std::mutex raise_mu;
-        static bool raised_on[64] = {false};
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        std::lock_guard<std::mutex> raise_lock(raise_mu);
-        bool &raised = raised_on[dev & 63];
-        if (!raised) {
-            const void *fns[2] = {reinterpret_cast<const void *>(&msda_level_grad_value<2>),
-                                  reinterpret_cast<const void *>(&msda_level_grad_value<4>)};
-            for (const void *fn : fns)
-                if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_CAP) != hipSuccess)
-                    return dfx::fail(DFX_ELAUNCH, "msda level grad_value: cannot raise the dynamic LDS limit");
-            raised = true;
-        }
-    }
+    if (const int rc = dfx::raise_lds_limit<&msda_level_grad_value<2>, &msda_level_grad_value<4>>("msda level grad_value",
+                                                                                                 (int)LDS_CAP))
+        return rc;
     const int nitems = N * 32;
     const GradValueArgs g{ref, off, logits, grad_out, grad_value, off_pitch, logit_pitch, H, W, Lq, PL, nitems};
     // persistent: at most one workgroup per CU, a multiple of 8 so that item & 7 (the head) is fixed per workgroup; the CU

@@ -146,9 +146,7 @@ inline long plane_tokens(int H, int W)
 // covers the rest), tuned only for that device.
 inline int persistent_grid()
 {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 8) n = 256;
-    return n / 8 * 8;
+    return cu_count() / 8 * 8;
 }
 
 }  // namespace level

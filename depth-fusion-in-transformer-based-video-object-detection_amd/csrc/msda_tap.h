@@ -9,7 +9,8 @@
 // gather phase as two conflict-free 16-byte broadcasts per point.
 //
 // Also the value-dtype helpers of the MSDA kernels (fp32, fp64, bf16, fp16): the arithmetic type of
-// a value dtype and the packed channel loads / stores.
+// a value dtype and the packed channel loads / stores; and the location arithmetic of the fused front
+// end (reference point, location rule), stated once for msda_fused_taps and msda_fused_bwd.
 #pragma once
 #include <hip/hip_bf16.h>
 
@@ -92,15 +93,42 @@ __device__ __forceinline__ Tap make_tap(float lx, float ly, float a, int H, int 
     return t;
 }
 
-// Phase A of the unfused wave-per-query forward (M = 8 heads, P = 4 points, LT levels): lane =
-// one (query, level, point, head) sample of the QW queries q0 .. q0+QW-1; it reads its (x, y)
-// pair and attention weight once and writes its tap to LDS slot ((qq*LT + l)*4 + p)*8 + head.
-// Queries at or past NQ get zero taps (offset 0, weight 0).
+// ---- phase A bookkeeping of the taps kernels (msda_fwd_taps, msda_fused_taps) -----------------
+// M = 8 heads, P = 4 points, LT levels; a wave stages the taps of QW queries per iteration, lane (+ 64 c) =
+// slot s = ((qq*LT + l)*4 + p)*8 + head of LDS.
 template <int LT>
 struct LevelDims {
-    int H[LT], W[LT], R[LT];     // (H_l, W_l, level_start_index[l]) of every level
+    int H[LT], W[LT], R[LT];     // (H_l, W_l, level_start_index[l]) of every level, filled by the kernel
 };
 
+template <int LT>
+struct Slot {
+    int hm, p, l, qq;            // head, point, level, query of the wave
+    __device__ __forceinline__ explicit Slot(int s)
+    {
+        const int ql = s >> 5;
+        hm = s & 7;
+        p = (s >> 3) & 3;
+        l = (LT == 1) ? 0 : ql % LT;
+        qq = (LT == 1) ? ql : ql / LT;
+    }
+};
+
+// Grid of a taps launch: 8 queries per workgroup and iteration; `iters` doubles (up to 8) while that
+// still leaves >= 2048 workgroups
+struct TapsGrid {
+    int iters;
+    unsigned blocks;
+};
+inline TapsGrid taps_grid(long nq)
+{
+    int iters = 1;
+    while (iters < 8 && nq / (8L * iters * 2) >= 2048) iters *= 2;
+    return {iters, (unsigned)((nq + 8L * iters - 1) / (8L * iters))};
+}
+
+// Phase A of the unfused forward: the lane reads its (x, y) pair and attention weight once and
+// writes its tap.  Queries at or past NQ get zero taps (offset 0, weight 0).
 template <int LT, int QW, unsigned ROW_BYTES>
 __device__ __forceinline__ void write_taps(const float *__restrict__ loc, const float *__restrict__ aw, int q0,
                                            int NQ, int lane, const LevelDims<LT> lv, uint4 *toff, float4 *tw)
@@ -108,10 +136,9 @@ __device__ __forceinline__ void write_taps(const float *__restrict__ loc, const 
     constexpr int TAPS = QW * LT * 32;    // taps per wave per iteration (multiple of 64)
 #pragma unroll
     for (int c = 0; c < TAPS / 64; ++c) {
-        const int s = c * 64 + lane;                 // slot = ((qq*LT + l)*4 + p)*8 + head
-        const int hm = s & 7, p = (s >> 3) & 3, ql = s >> 5;
-        const int l = (LT == 1) ? 0 : ql % LT, qq = (LT == 1) ? ql : ql / LT;
-        const int qi = q0 + qq;
+        const int s = c * 64 + lane;
+        const Slot<LT> sl(s);
+        const int hm = sl.hm, p = sl.p, l = sl.l, qi = q0 + sl.qq;
         Tap t;
         if (qi < NQ) {
             const long e = (((long)qi * 8 + hm) * LT + l) * 4 + p;
@@ -128,6 +155,50 @@ __device__ __forceinline__ void write_taps(const float *__restrict__ loc, const 
         toff[s] = t.off;
         tw[s] = t.w;
     }
+}
+
+// ---- the fused front end's location arithmetic (msda_fused_taps; msda_fused_bwd calls the same routines) ----
+// Reference point of one (query, level): (x, y) and, for ref_dim 4, the box (w, h) that scales the offsets
+struct RefPoint {
+    float x, y, kx, ky;
+};
+template <int REFDIM>
+__device__ __forceinline__ RefPoint load_ref(const float *__restrict__ rp)
+{
+    if constexpr (REFDIM == 2) {
+        return {rp[0], rp[1], 0.f, 0.f};
+    } else {
+        const float4 rr = *reinterpret_cast<const float4 *>(rp);
+        return {rr.x, rr.y, rr.z, rr.w};
+    }
+}
+
+// Sampling location of one point from its offset (ox, oy) on a W x H level (ms_deform_attn.py:102-110):
+//   ref_dim 2: ref + off / (W, H)          ref_dim 4: ref_xy + off / P * ref_wh * 0.5   (P = 4)
+template <int REFDIM>
+__device__ __forceinline__ float2 sample_location(const RefPoint &r, float ox, float oy, int W, int H)
+{
+    if (REFDIM == 2) return make_float2(r.x + ox / (float)W, r.y + oy / (float)H);
+    return make_float2(r.x + ox / 4.f * r.kx * 0.5f, r.y + oy / 4.f * r.ky * 0.5f);
+}
+
+// ---- reductions of the (head m = lane >> 3, channel quad cg = lane & 7) lane map (msda_bwd_m8d32, msda_fused_bwd) ----
+__device__ __forceinline__ float head_sum(float v)
+{
+    // sum over the 8 lanes (lane&7) that share one head
+    v += __shfl_xor(v, 1, 64);
+    v += __shfl_xor(v, 2, 64);
+    v += __shfl_xor(v, 4, 64);
+    return v;
+}
+
+__device__ __forceinline__ float all_heads_sum(float v)
+{
+    // v is uniform over the 8 lanes of a head: sum over the 8 heads of the wave
+    v += __shfl_xor(v, 8, 64);
+    v += __shfl_xor(v, 16, 64);
+    v += __shfl_xor(v, 32, 64);
+    return v;
 }
 
 __device__ __forceinline__ void fma4(float4 &acc, float w, const float4 &v)
@@ -184,6 +255,44 @@ __device__ __forceinline__ float4 gather_query(const char *__restrict__ vb, unsi
         }
     }
     return acc;
+}
+
+// ---- host side of the two fused entry points (msda_fused.hip, msda_fused_backward.hip) ----
+// What dfx_msda_fused_forward_f32 and dfx_msda_fused_backward_f32 both check (same return values as check_dims).
+// `what` heads the error texts, `unfused` is the entry point that takes the geometries the fused kernels do not;
+// `rows` is the [N*Lq, 256] operand next to value: out in the forward, grad_out in the backward.
+inline int check_fused(const char *what, const char *unfused, const float *value, const int64_t *shapes, const int64_t *lsi,
+                       const float *ref, int ref_dim, const float *off, long off_stride, const float *logits,
+                       long logit_stride, const float *rows, int N, int S, int M, int D, int L, int Lq, int P)
+{
+    const int rc = check_dims(value, shapes, lsi, off, logits, rows, N, S, M, D, L, Lq, P);
+    if (rc != 0) return rc;
+    if (!ref) return fail(DFX_EINVAL, "%s: null reference points", what);
+    if (ref_dim != 2 && ref_dim != 4) return fail(DFX_EINVAL, "%s: ref_dim must be 2 or 4, got %d", what, ref_dim);
+    if (M != 8 || D != 32 || P != 4 || L < 1 || L > 4)
+        return fail(DFX_EINVAL, "msda fused: only M=8, D=32, P=4, 1<=L<=4 is fused (got M=%d D=%d P=%d L=%d); use %s",
+                    M, D, P, L, unfused);
+    if (off_stride < (long)M * L * P * 2 || logit_stride < (long)M * L * P || ((off_stride | logit_stride) & 3))
+        return fail(DFX_EINVAL, "%s: bad row strides", what);
+    if (!aligned16(value) || !aligned16(rows) || !aligned16(off) || !aligned16(logits) || (ref_dim == 4 && !aligned16(ref)))
+        return fail(DFX_EINVAL, "%s: buffers must be 16-byte aligned", what);
+    if ((long)N * Lq >= (1L << 28) || (long)S * 1024 >= (1L << 32)) return fail(DFX_ERANGE, "%s: problem too large", what);
+    return 0;
+}
+
+// The (L, ref_dim) instantiation of a fused kernel: calls f(integral_constant<int, L>, integral_constant<int, ref_dim>).
+template <typename F>
+inline int dispatch_fused(int L, int ref_dim, F f)
+{
+    auto levels = [&](auto rd) {
+        switch (L) {
+            case 1: return f(std::integral_constant<int, 1>(), rd);
+            case 2: return f(std::integral_constant<int, 2>(), rd);
+            case 3: return f(std::integral_constant<int, 3>(), rd);
+            default: return f(std::integral_constant<int, 4>(), rd);
+        }
+    };
+    return ref_dim == 2 ? levels(std::integral_constant<int, 2>()) : levels(std::integral_constant<int, 4>());
 }
 
 }  // namespace dfx
