@@ -697,3 +697,40 @@ extern "C" int dfx_gemm_splitk_f32(const float *A, long lda, const float *B, lon
                        (long)M * N, N, bias, bias_per_row, R, ldr, act, C, ldc);
     return dfx::check_launch("splitk_reduce_kernel");
 }
+
+// dW[Co,Ci] = sum_n sum_p dZ[n,Co,p] X[n,Ci,p]: the weight gradient of a 1x1 convolution (include/dfx_gemm.h).  Per image it is
+// the [M,K] x [N,K]^T product above with the pixels as K, so the images ride the batch axis of the split-K launch: slice
+// z = image * splits + range writes slab z, and the reduction adds the slabs in that (ascending) order.
+extern "C" int dfx_conv1x1_wgrad_f32(const float *dZ, long strideZ, const float *X, long strideX, float *dW, int Co, int Ci,
+                                     int HW, int batch, int splits, float *workspace, void *stream)
+{
+    if (Co < 0 || Ci < 0 || HW < 0 || batch < 0 || splits < 1) return dfx::fail(DFX_EINVAL, "conv1x1_wgrad: bad dimension");
+    if ((long)Co * Ci == 0) return DFX_OK;
+    if (!dW || ((long)batch * HW > 0 && (!dZ || !X))) return dfx::fail(DFX_EINVAL, "conv1x1_wgrad: null pointer");
+    if ((Co & 3) || (Ci & 3) || (HW & 3) || (strideZ & 3) || (strideX & 3) || !dfx::aligned16(dZ) || !dfx::aligned16(X) ||
+        !dfx::aligned16(dW) || !dfx::aligned16(workspace))
+        return dfx::fail(DFX_EINVAL, "conv1x1_wgrad: Co, Ci, H*W and the image strides must be multiples of 4, buffers 16-byte aligned");
+    if ((long)Co * HW * 4 >= (1L << 31) || (long)Ci * HW * 4 >= (1L << 31) || (long)Co * Ci * 4 >= (1L << 31))
+        return dfx::fail(DFX_ERANGE, "conv1x1_wgrad: an operand exceeds 2 GiB per image");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if ((long)batch * HW == 0) {           // empty sums
+        if (hipMemsetAsync(dW, 0, (size_t)Co * Ci * 4, st) != hipSuccess) return dfx::fail(DFX_ELAUNCH, "conv1x1_wgrad: memset failed");
+        return DFX_OK;
+    }
+    const int kper = ((HW + splits - 1) / splits + 15) / 16 * 16;      // whole 16-deep steps per range ...
+    splits = (HW + kper - 1) / kper;                                    // ... and no range empty
+    const long slabs = (long)batch * splits;
+    if (slabs > 65535) return dfx::fail(DFX_ERANGE, "conv1x1_wgrad: too many images x ranges");
+    if (slabs > 1 && !workspace) return dfx::fail(DFX_EINVAL, "conv1x1_wgrad: more than one image or range needs a workspace");
+    Args g = product(dZ, HW, X, HW, slabs > 1 ? workspace : dW, Ci, Co, Ci, HW);
+    g.strideA = strideZ, g.strideB = strideX;
+    g.strideC = (long)Co * Ci;                                         // one slab per (image, range)
+    g.wide_epilogue = 1;
+    g.splits = splits, g.kper = kper;
+    const int rc = choose_and_launch(g, batch, 0, st);
+    if (rc != DFX_OK || slabs == 1) return rc;
+    const long quads = (long)Co * Ci / 4;
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, st, workspace, (int)slabs,
+                       (long)Co * Ci, Ci, (const float *)nullptr, 0, (const float *)nullptr, 0L, 0, dW, (long)Ci);
+    return dfx::check_launch("splitk_reduce_kernel");
+}

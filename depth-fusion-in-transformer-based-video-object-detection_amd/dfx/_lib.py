@@ -58,12 +58,17 @@ SIGNATURES = {
     "dfx_conv1x1_chain_f32": [_p, _p, _l, _i, _p, _l, _i, _p, _p, _l, _p, _l, _p, _p, _p, _l, _i, _i, _i, _i, _i, _p],
     # dY, ldy, X, ldx, dW, ldw, db | NULL, M, N, K, splits, workspace | NULL, stream (csrc/gemm_wgrad.hip)
     "dfx_gemm_wgrad_f32": [_p, _l, _p, _l, _p, _l, _p, _i, _i, _i, _i, _p, _p],
+    # dZ, image stride, X, image stride, dW, Co, Ci, HW, batch, splits, workspace | NULL, stream (csrc/gemm_f32.hip)
+    "dfx_conv1x1_wgrad_f32": [_p, _l, _p, _l, _p, _i, _i, _i, _i, _i, _p, _p],
     # include/dfx_fused.h: x, bias, residual, out, N, C, HW, relu, stream
     "dfx_bias_act_nchw_f32": [_p, _p, _p, _p, _i, _i, _l, _i, _p],
     "dfx_bias_relu_maxpool_f32": [_p, _p, _p, _i, _i, _i, _i, _p],
     "dfx_add_layernorm_f32": [_p, _p, _p, _p, _p, _l, _i, ctypes.c_float, _p],
     "dfx_box_refine_f32": [_p, _p, _i, _p, _l, ctypes.c_float, _p],
     "dfx_group_norm_f32": [_p, _p, _p, _p, _p, _i, _i, _l, _i, ctypes.c_float, _i, _p],
+    # dy, x, stats, gamma, dx | NULL, dgamma | NULL, dbeta | NULL, workspace, N, C, HW, groups, dy_tokens, stream
+    # (csrc/groupnorm_backward.hip)
+    "dfx_group_norm_backward_f32": [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _l, _i, _i, _p],
     # include/dfx_conv.h
     "dfx_conv2d_igemm_f32": [_p, _p, _p, _p, _p] + [_i] * 14 + [_l, _p],
     "dfx_conv2d_tile_fits": [_i] * 6,

@@ -810,6 +810,89 @@ def conv1x1(x, weight, bias=None, residual=None, relu=False, stride=1):
     return out
 
 
+# ---- 1x1 convolution in grad mode (include/dfx_gemm.h, dfx_conv1x1_wgrad_f32) -------------------------------------------------
+# (bound here for the autograd node and its backward, as ``_linear_forward`` is: ``ops.conv1x1`` by name is a module's route)
+_conv1x1_forward = conv1x1
+
+
+def _conv1x1_wgrad_splits(Co, Ci, HW, batch):
+    """Pixel ranges per image of the weight gradient dW[Co,Ci] = sum_n dZ[n] X[n]^T (pure host rule, ``_wgrad_splits``' with the
+    images as a second source of workgroups): tiles x images x ranges stay within one resident round of workgroups (3 per CU
+    for the 128 x 128 tile, 4 for the 64 x 128 one of Co <= 64), a range is at least ``_WGRAD_MIN_STEPS`` 16-deep steps long
+    and images x ranges stay within ``_WGRAD_MAX_RANGES`` slabs.  Both constants are taken over from ``_wgrad_splits`` as
+    they are; they were measured for Linear layers and not re-tuned for this product.  The result is what the library will
+    run: no range is empty."""
+    if HW <= 0 or batch <= 0:
+        return 1
+    if Co <= 64:
+        tiles, slots = -(-Ci // 128), 1024
+    else:
+        tiles, slots = -(-Co // 128) * -(-Ci // 128), 768
+    want = max(1, min(-(-HW // 16) // _WGRAD_MIN_STEPS, slots // (tiles * batch), _WGRAD_MAX_RANGES // batch))
+    return _wgrad_ranges(HW, want)[1]
+
+
+def conv1x1_backward(grad_out, x, weight, need_x=True, need_w=True, need_b=True, splits=None):
+    """Gradients of ``y = conv1x1(x, weight, bias)``: -> (grad_x | None, grad_w | None, grad_b | None), fp32, fresh tensors.
+    grad_out [N,Co,H,W] and x [N,Ci,H,W] contiguous, weight [Co,Ci(,1,1)]; Co, Ci and H*W multiples of 4.
+    grad_x[n] = weight^T x grad_out[n] is ``dfx_gemm_f32`` with ``weight.t().contiguous()`` as A and grad_out as the [K,N]
+    operand of every image.  grad_w comes from ``dfx_conv1x1_wgrad_f32`` (``_conv1x1_wgrad_splits`` pixel ranges per image, or
+    ``splits``; the slabs are added in ascending (image, range) order: two calls give the same bits) and has weight's shape.
+    grad_b = grad_out.sum((0, 2, 3)) is the library's reduction: the product kernel stages grad_out in its A operand's
+    K-contiguous layout, where a column sum would cost the flagship GEMM registers it has none to spare."""
+    Nb, Ci, H, W = x.shape
+    Co, HW = weight.shape[0], H * W
+    w2 = weight.reshape(Co, -1)
+    _check_inputs([("grad_out", grad_out), ("x", x), ("weight", w2)])
+    _require(grad_out.dtype == torch.float32 and x.dtype == torch.float32 and w2.dtype == torch.float32,
+             "conv1x1_backward is implemented for float32")
+    _require(grad_out.shape == (Nb, Co, H, W) and w2.shape[1] == Ci and Co % 4 == 0 and Ci % 4 == 0 and HW % 4 == 0,
+             "conv1x1_backward: grad_out [N,Co,H,W], x [N,Ci,H,W] with Co, Ci and H*W multiples of 4")
+    dev = x.device
+    grad_x = grad_w = grad_b = None
+    if need_x:
+        grad_x = _conv1x1_forward(grad_out, w2.t().contiguous())
+    if need_w:
+        grad_w = torch.empty(weight.shape, dtype=torch.float32, device=dev)
+        if Nb * HW == 0:
+            grad_w.zero_()
+        else:
+            n = _conv1x1_wgrad_splits(Co, Ci, HW, Nb) if splits is None else _wgrad_ranges(HW, max(1, int(splits)))[1]
+            ws = torch.empty((Nb * n * Co * Ci,), dtype=torch.float32, device=dev) if Nb * n > 1 else None
+            _call("conv1x1_backward (grad_w)", "dfx_conv1x1_wgrad_f32", dev, grad_out.data_ptr(), Co * HW, x.data_ptr(), Ci * HW,
+                  grad_w.data_ptr(), Co, Ci, HW, Nb, n, _ptr(ws))
+    if need_b:
+        grad_b = grad_out.sum((0, 2, 3))
+    return grad_x, grad_w, grad_b
+
+
+class _Conv1x1Function(torch.autograd.Function):
+    """apply(x, weight, bias | None): saves the contiguous x and the weight, as nn.Conv2d does."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        ctx.save_for_backward(x, weight)
+        return _conv1x1_forward(x, weight, bias)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        x, weight = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        # (looked up at call time: tests wrap it)
+        return conv1x1_backward(grad_output.contiguous(), x, weight, need_x=need[0], need_w=need[1], need_b=need[2])
+
+
+def conv1x1_train(x, weight, bias=None):
+    """``conv1x1(x, weight, bias)`` that trains: with grad mode on and x, weight or bias requiring a gradient the result
+    carries it back through ``conv1x1_backward`` - computed for exactly the inputs that ask for one; otherwise no autograd
+    node is made.  Either way the forward is ``conv1x1`` itself (the same bits).  Co, Ci and H*W multiples of 4."""
+    if torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad or (bias is not None and bias.requires_grad)):
+        _require(weight.shape[0] % 4 == 0, "conv1x1_train: Co must be a multiple of 4")
+        return _Conv1x1Function.apply(x.contiguous(), weight, bias)
+    return conv1x1(x, weight, bias)
+
+
 def conv1x1_pair(x1, x2, weight, bias=None, relu=False):
     """relu?(weight x [x1 ; x2] + bias): two NCHW inputs of one map size concatenated along the channels inside the
     product (include/dfx_gemm.h, dfx_conv1x1_pair_f32) - a bottleneck's last 1x1 convolution and its stride-1
@@ -1191,16 +1274,83 @@ class ConvPlan:
         return y
 
 
+def _group_norm_forward(x, weight, bias, groups, eps, tokens_out):
+    """-> (y, stats): y [N,H*W,C] with tokens_out, else [N,C,H,W]; stats [N*groups*2] (mean, rstd) as the backward reads them"""
+    _check_inputs([("x", x), ("weight", weight), ("bias", bias)])
+    _require(x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == weight.numel(), "group_norm: fp32 NCHW")
+    N, C, H, W = x.shape
+    stats = torch.empty(N * groups * 2, dtype=torch.float32, device=x.device)
+    y = torch.empty((N, H * W, C) if tokens_out else (N, C, H, W), dtype=torch.float32, device=x.device)
+    _call("group_norm", "dfx_group_norm_f32", x.device, x.data_ptr(), weight.data_ptr(), bias.data_ptr(),
+          stats.data_ptr(), y.data_ptr(), N, C, H * W, groups, float(eps), int(bool(tokens_out)))
+    return y, stats
+
+
+GN_BWD_CHUNKS = 16      # DFX_GN_BWD_CHUNKS of include/dfx_fused.h
+
+
+def group_norm_backward(grad_out, x, stats, gamma, groups, tokens=False, need_x=True, need_gamma=True, need_beta=True):
+    """Gradients of ``group_norm``: -> (grad_x | None, grad_gamma | None, grad_beta | None), fp32, fresh tensors
+    (include/dfx_fused.h, dfx_group_norm_backward_f32: two streaming launches, no atomics, the same bits every call).
+    x [N,C,H,W] contiguous, stats as the forward wrote them, gamma [C]; grad_out contiguous, [N,C,H,W] or - ``tokens`` -
+    [N,H*W,C], the memory layout of the forward's tokens_out result: it is read as it lies, through an LDS transpose."""
+    N, C, H, W = x.shape
+    _check_inputs([("grad_out", grad_out), ("x", x), ("stats", stats), ("gamma", gamma)])
+    _require(grad_out.dtype == torch.float32 and x.dtype == torch.float32 and gamma.numel() == C and C % groups == 0
+             and stats.numel() == N * groups * 2, "group_norm_backward: fp32, gamma [C], stats [N*groups*2]")
+    _require(tuple(grad_out.shape) == ((N, H * W, C) if tokens else (N, C, H, W)), "group_norm_backward: grad_out [N,H*W,C] (tokens) or [N,C,H,W]")
+    dev = x.device
+    new = torch.zeros if N * H * W == 0 else torch.empty
+    grad_x = torch.empty_like(x) if need_x else None
+    grad_gamma = new((C,), dtype=torch.float32, device=dev) if need_gamma else None
+    grad_beta = new((C,), dtype=torch.float32, device=dev) if need_beta else None
+    if N * H * W > 0 and (need_x or need_gamma or need_beta):
+        ws = torch.empty((N * C * 2 * GN_BWD_CHUNKS,), dtype=torch.float32, device=dev)
+        _call("group_norm_backward", "dfx_group_norm_backward_f32", dev, grad_out.data_ptr(), x.data_ptr(), stats.data_ptr(),
+              gamma.data_ptr(), _ptr(grad_x), _ptr(grad_gamma), _ptr(grad_beta), ws.data_ptr(), N, C, H * W, groups, int(bool(tokens)))
+    return grad_x, grad_gamma, grad_beta
+
+
+class _GroupNormFunction(torch.autograd.Function):
+    """apply(x, weight, bias, groups, eps, tokens_out) -> y as ``_group_norm_forward`` lays it out; saves x, stats and the weight."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, groups, eps, tokens_out):
+        y, stats = _group_norm_forward(x, weight, bias, groups, eps, tokens_out)
+        ctx.save_for_backward(x, stats, weight)
+        ctx.groups, ctx.tokens_out = groups, tokens_out
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        x, stats, weight = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        # the kernel reads either layout as it lies: a gradient that is contiguous in the other one (token-major flowing back
+        # into an NCHW result or the reverse) is handed over under that layout's flag, not copied
+        N, C, H, W = x.shape
+        g, tokens = grad_output, ctx.tokens_out
+        if not g.is_contiguous():
+            other = g.transpose(1, 2) if tokens else g.permute(0, 2, 3, 1)          # [N,C,H*W] / [N,H,W,C]
+            if other.is_contiguous():
+                g, tokens = other.reshape((N, C, H, W) if tokens else (N, H * W, C)), not tokens
+            else:
+                g = g.contiguous()
+        # (looked up at call time: tests wrap it)
+        gx, gg, gb = group_norm_backward(g, x, stats, weight, ctx.groups, tokens=tokens, need_x=need[0], need_gamma=need[1],
+                                         need_beta=need[2])
+        return gx, gg, gb, None, None, None
+
+
 def group_norm(x, norm, tokens_out=False):
     """nn.GroupNorm ``norm`` applied to x [N,C,H,W] (contiguous NCHW) in two streaming launches
     (include/dfx_fused.h, dfx_group_norm_f32).  tokens_out: the result is written token-major [N,H*W,C] and
     returned as an NCHW-shaped VIEW of that memory, so ``y.flatten(2).transpose(1, 2)`` - what the transformer
-    does next - is already contiguous and costs nothing."""
-    _check_inputs([("x", x), ("weight", norm.weight), ("bias", norm.bias)])
-    _require(x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == norm.num_channels, "group_norm: fp32 NCHW")
-    N, C, H, W = x.shape
-    stats = torch.empty(N * norm.num_groups * 2, dtype=torch.float32, device=x.device)
-    y = torch.empty((N, H * W, C) if tokens_out else (N, C, H, W), dtype=torch.float32, device=x.device)
-    _call("group_norm", "dfx_group_norm_f32", x.device, x.data_ptr(), norm.weight.data_ptr(), norm.bias.data_ptr(),
-          stats.data_ptr(), y.data_ptr(), N, C, H * W, norm.num_groups, float(norm.eps), int(bool(tokens_out)))
-    return y.transpose(1, 2).unflatten(2, (H, W)) if tokens_out else y
+    does next - is already contiguous and costs nothing.
+    With grad mode on and x or a parameter of ``norm`` requiring a gradient the same forward runs under an autograd node
+    whose backward is ``group_norm_backward`` (computed for exactly the inputs that ask); otherwise no node is made."""
+    if torch.is_grad_enabled() and (x.requires_grad or norm.weight.requires_grad or norm.bias.requires_grad):
+        y = _GroupNormFunction.apply(x, norm.weight, norm.bias, norm.num_groups, float(norm.eps), bool(tokens_out))
+    else:
+        y = _group_norm_forward(x, norm.weight, norm.bias, norm.num_groups, norm.eps, tokens_out)[0]
+    return y.transpose(1, 2).unflatten(2, (x.shape[2], x.shape[3])) if tokens_out else y

@@ -16,6 +16,7 @@ from torch import nn
 from util.memo import memo_on
 from util.misc import NestedTensor
 
+from .fused import needs_grad
 from .position_encoding import build_position_encoding
 from .resnet import ResNet50
 
@@ -81,13 +82,21 @@ class FusionBackboneBase(nn.Module):
         m = tensor_list.mask
         assert m is not None, "Mask should not be None"
         body = self.body
-        fused = self.fused_inference and not torch.is_grad_enabled()
         own = hasattr(body, "stem")      # models.resnet.ResNet50; any torchvision-style body works op by op (ref :112-131)
-        x = body.stem(x, fused) if own else body.maxpool(body.relu(body.bn1(body.conv1(x))))
+        # The fused route is decided per part (the stem, then each stage): a part runs fused while nothing in it needs a
+        # gradient, grad mode or not - the frozen body of the fine-tuning recipes (ref main.py:311-316, main_multi.py:381-385,
+        # lr_backbone 0) and a frozen prefix alike.  The first part that trains runs op by op; its output requires grad, so
+        # every part behind it does too.  (Grad mode under autocast keeps the op-by-op route, as before.)
+        amp = torch.is_grad_enabled() and torch.is_autocast_enabled()
+        fused = lambda params, t: self.fused_inference and not amp and not needs_grad(params, t)      # noqa: E731
+        if own:
+            x = body.stem(x, fused(list(body.conv1.parameters()) + list(body.bn1.parameters()), x))
+        else:
+            x = body.maxpool(body.relu(body.bn1(body.conv1(x))))
         out: Dict[str, NestedTensor] = {}
         wanted = set(self.return_layers.values()) if self.return_interm_layers else set()
         for key, stage in (("0", body.layer1), ("1", body.layer2), ("2", body.layer3), ("3", body.layer4)):
-            x = body.run_stage(stage, x, fused) if own else stage(x)
+            x = body.run_stage(stage, x, fused(stage, x)) if own else stage(x)
             if key == "3":
                 # the last stage always reports; under key "3" only if such a key was requested
                 out["3" if key in wanted else "0"] = NestedTensor(x, _resize_mask(m, x.shape[-2:]))

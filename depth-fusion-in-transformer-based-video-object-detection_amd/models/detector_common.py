@@ -10,6 +10,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from dfx import ops as _ops
+from models import fused as _fused
 from models.fused import Linear
 
 from util import box_ops
@@ -48,11 +49,20 @@ class MLP(nn.Module):
 class _ConvGN(nn.Sequential):
     """Conv2d + GroupNorm(32) of the input projections (ref deformable_detr_single.py:101-125).  GPU inference:
     the convolution on the hand-written kernels (1x1: MFMA GEMM with the bias in its epilogue; 3x3/2 of the extra
-    levels: implicit GEMM), GroupNorm as two streaming launches that write token-major memory (dfx.ops.group_norm)."""
+    levels: implicit GEMM), GroupNorm as two streaming launches that write token-major memory (dfx.ops.group_norm).
+    That route is taken whenever nothing needs a gradient (models.fused.needs_grad), grad mode or not.  GPU training (fp32,
+    no autocast, no hooks on the two modules, a map of at least models.fused.CONVGN_TRAIN_MIN_PIXELS pixels): a plain 1x1
+    convolution runs as dfx.ops.conv1x1_train, any other one as its nn.Conv2d, and the GroupNorm as dfx.ops.group_norm with
+    its autograd node - the forward of inference, the backward on the GEMM, dfx_conv1x1_wgrad_f32 and
+    csrc/groupnorm_backward.hip.  Smaller maps, and models.fused.CONVGN_TRAIN off, keep nn.Sequential."""
 
     def forward(self, x):
         conv, norm = self[0], self[1]
-        if not (x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled()):
+        if not (x.is_cuda and x.dtype == torch.float32):
+            return super().forward(x)
+        if _fused.needs_grad(self, x):
+            return self._forward_train(x)
+        if torch.is_grad_enabled() and torch.is_autocast_enabled():
             return super().forward(x)
         x = x.contiguous()
         hw = x.shape[2] * x.shape[3]
@@ -65,6 +75,20 @@ class _ConvGN(nn.Sequential):
                                                  groups=conv.groups, padding_mode=conv.padding_mode))
             y = self._plan[1](x)
         return _ops.group_norm(y, norm, tokens_out=True)
+
+    def _forward_train(self, x):
+        """Grad mode with something to differentiate (see the class docstring)."""
+        conv, norm = self[0], self[1]
+        if not (_fused.CONVGN_TRAIN and x.shape[0] * x.shape[2] * x.shape[3] >= _fused.CONVGN_TRAIN_MIN_PIXELS
+                and not torch.is_autocast_enabled() and norm.affine
+                and all(p.dtype == torch.float32 and p.device == x.device for p in self.parameters())
+                and not _fused.has_hooks(conv) and not _fused.has_hooks(norm)):
+            return super().forward(x)
+        x = x.contiguous()
+        plain = (conv.kernel_size == (1, 1) and conv.stride == (1, 1) and conv.padding == (0, 0) and conv.groups == 1
+                 and x.shape[1] % 4 == 0 and conv.out_channels % 4 == 0 and (x.shape[2] * x.shape[3]) % 4 == 0)
+        y = _ops.conv1x1_train(x, conv.weight, conv.bias) if plain else conv(x)
+        return _ops.group_norm(y.contiguous(), norm, tokens_out=True)
 
 
 def _conv_gn(cin, cout, kernel_size=1, **kw):

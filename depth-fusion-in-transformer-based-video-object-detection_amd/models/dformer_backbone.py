@@ -16,6 +16,7 @@ from dfx import ops as _ops
 from util.memo import memo_on
 from util.misc import NestedTensor
 
+from .fused import needs_grad
 from .position_encoding import build_position_encoding
 
 
@@ -76,7 +77,10 @@ class DFormerBackbone(nn.Module):
         assert m is not None, "Input mask is None."
         out: Dict[str, NestedTensor] = {}
         stages = self.depth_backbone.downsample_layers_e[:-1]        # the 4th stage is never run
-        if (not self.return_interm_layers and x.is_cuda and not torch.is_grad_enabled()
+        # (nothing to differentiate - no_grad, or the all-frozen backbones of the TransVOD++ recipe, ref main_multi.py:381-385;
+        # grad mode under autocast keeps the module route, as before)
+        if (not self.return_interm_layers and x.is_cuda and not needs_grad(stages, x)
+                and not (torch.is_grad_enabled() and torch.is_autocast_enabled())
                 and not any(mod.training for mod in stages.modules() if isinstance(mod, nn.BatchNorm2d))):
             x = self._forward_folded(stages, x)
             out["0"] = NestedTensor(x, _resize_mask(m, x.shape[-2:]))

@@ -30,6 +30,27 @@ LINEAR_TRAIN = os.environ.get("DFX_LINEAR_TRAIN", "1") != "0"
 # (256 -> 32768) that sum is 5.0e-6 from fp64 against the 2.3e-6 tests/test_dynconv_backward_gpu.py allows (4 x the CPU's
 # blocked fp32 sum), so wider layers stay on nn.Linear (profiles/r14_linear_train.txt).
 LINEAR_TRAIN_MAX_OUT_FEATURES = 1024
+# The input projections (models.detector_common._ConvGN) in grad mode on dfx.ops.conv1x1_train and the GroupNorm backward
+# kernels (csrc/groupnorm_backward.hip); DFX_CONVGN_TRAIN=0 keeps nn.Sequential there (A/B measurements).  Read once at import.
+CONVGN_TRAIN = os.environ.get("DFX_CONVGN_TRAIN", "1") != "0"
+# The smallest map (images x H x W pixels) at which that route MEASURED faster than nn.Sequential beyond the repetition spread:
+# 12 frames of 50 x 84 (1.05x at 2048 -> 256, 1.15x at 128 -> 256; 32 frames 1.04x / 1.10x).  8 frames tie and 4 frames are
+# 8-15 % slower - a handful of short launches issued from Python against the library's C++ nodes - so smaller maps keep
+# nn.Sequential (tools/bench_convgn_train.py, profiles/r15_convgn_train.txt).
+CONVGN_TRAIN_MIN_PIXELS = 12 * 50 * 84
+
+
+def needs_grad(part, *tensors):
+    """Does running ``part`` (a module, or an iterable of parameters) on ``tensors`` have anything to differentiate?  True only
+    when grad mode is on and one of the tensors or one of the part's parameters requires a gradient.  The front of the detector
+    routes on this, not on grad mode alone: a frozen backbone under a training step keeps its fused inference route, and its
+    outputs carry no grad_fn (``MSDeformAttn._route`` decides the same way)."""
+    if not torch.is_grad_enabled():
+        return False
+    if any(t is not None and t.requires_grad for t in tensors):
+        return True
+    params = part.parameters() if isinstance(part, nn.Module) else part
+    return any(p.requires_grad for p in params)
 
 
 class Linear(nn.Linear):

@@ -15,6 +15,8 @@ import os
 
 from dfx import ops as _ops
 
+from .fused import needs_grad
+
 _PAIR_SHORTCUT = os.environ.get("DFX_PAIR_SHORTCUT", "1") == "1"      # A/B switch of the fused conv3 + shortcut product
 _CONV_CHAIN = os.environ.get("DFX_CONV_CHAIN", "1") == "1"            # A/B switch of conv3 + the next block's conv1 in one launch
 # widest conv1 the chain takes: 256 output channels (layer2[3] -> layer3[0]) leave the fused kernel one workgroup per CU and
@@ -195,11 +197,15 @@ class ResNet50(nn.Module):
         carry, self._chain_carry = self.__dict__.get("_chain_carry"), None
         z = carry[1] if carry is not None and carry[0] is x else None
         follower = {id(self.layer1): self.layer2, id(self.layer2): self.layer3}.get(id(stage)) if _CONV_CHAIN else None
+        # a stage that trains runs op by op (models.backbone_scratch.FusionBackboneBase.forward): its first conv1 is not
+        # computed here from detached folded weights, and no carry is left waiting for it (this stage's output carries no
+        # gradient, so the follower's own parameters decide)
+        across = follower is not None and not needs_grad(follower)
         blocks = list(stage)
         for i, block in enumerate(blocks):
             succ = None
             if follower is not None:
-                succ = blocks[i + 1] if i + 1 < len(blocks) else follower[0]
+                succ = blocks[i + 1] if i + 1 < len(blocks) else (follower[0] if across else None)
             nxt = succ.chain_conv1() if succ is not None else None
             if nxt is None:
                 x, z = block.forward_fused(x, z), None

@@ -52,6 +52,23 @@ int dfx_box_refine_f32(const float *delta, const float *ref, int ref_dim, float 
 int dfx_group_norm_f32(const float *x, const float *gamma, const float *beta, float *stats, float *y,
                        int N, int C, long HW, int groups, float eps, int tokens_out, void *stream);
 
+/* Backward of dfx_group_norm_f32 (csrc/groupnorm_backward.hip), what autograd computes for the nn.GroupNorm of the input
+ * projections when they train.  With xh = (x - mean) * rstd from the forward's ``stats``, m = (C/groups) * HW,
+ * a_g = sum_{c in g, p} gamma[c] dy and b_g = sum_{c in g, p} gamma[c] dy xh:
+ *   dx[n,c,p]  = rstd * (gamma[c] * dy - a_g / m - xh * b_g / m)      [N,C,HW]
+ *   dgamma[c]  = sum_{n,p} dy * xh                                    [C]
+ *   dbeta[c]   = sum_{n,p} dy                                         [C]
+ * Each of the three outputs may be NULL and is then not computed; the others are overwritten, never accumulated into.
+ *   dy: dy_tokens = 0 -> [N,C,HW];  dy_tokens = 1 -> [N,HW,C], the layout of the forward's tokens_out result
+ *   x [N,C,HW], stats [N*groups*2] as the forward left them, gamma [C]
+ *   workspace: N * C * 2 * DFX_GN_BWD_CHUNKS floats, caller-owned (per-image, per-channel partial sums)
+ * No atomics; partial sums are added in ascending pixel-chunk, channel and image order: two calls give the same bits.
+ * Argument checks as dfx_group_norm_f32; N * HW == 0 returns DFX_OK without a launch. */
+#define DFX_GN_BWD_CHUNKS 16
+int dfx_group_norm_backward_f32(const float *dy, const float *x, const float *stats, const float *gamma,
+                                float *dx, float *dgamma, float *dbeta, float *workspace,
+                                int N, int C, long HW, int groups, int dy_tokens, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

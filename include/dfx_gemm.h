@@ -76,6 +76,18 @@
  * N, K, ldy, ldx and ldw multiples of 4 (ld >= the row), dY, X, dW and workspace 16-byte aligned, else DFX_EINVAL.  Only one
  * range has to stay below 2 GiB (rows per range * max(ldy, ldx) * 4 bytes, else DFX_ERANGE); the operands may be larger.
  * N * K == 0 returns DFX_OK without a launch; M == 0 writes zeros to dW and db.
+ *
+ * dfx_conv1x1_wgrad_f32: the weight gradient of a 1x1 convolution Z[n] = W x X[n] (the input projections, Conv2d(2048, 256, 1)
+ * and Conv2d(128, 256, 1), /root/reference/models/deformable_detr_single.py:101-125, when they train):
+ *   dW[co][ci] = sum_n sum_p dZ[n][co][p] X[n][ci][p]     [Co, Ci] packed
+ * dZ [batch,Co,HW], X [batch,Ci,HW] with image strides in floats.  It is the b_is_kn = 0 product of dfx_gemm_splitk_f32
+ * with the batch turned on: ONE product launch over images x pixel ranges of whole 16-deep steps (``splits`` ranges per
+ * image, clamped so that none is empty) writes partial [Co,Ci] slabs to ``workspace`` (batch * splits * Co * Ci floats,
+ * caller-owned, 16-byte aligned), one reduction launch adds them in ascending (image, range) order: no atomics, two calls
+ * give the same bits, dW is overwritten.  A single image in a single range stores directly and ``workspace`` may be NULL.
+ * Co, Ci, HW and the strides multiples of 4, dZ, X, dW and workspace 16-byte aligned, else DFX_EINVAL; one image's operand
+ * (and dW) must stay below 2 GiB, batch * splits at most 65535, else DFX_ERANGE.  Co * Ci == 0 returns DFX_OK without a
+ * launch; batch * HW == 0 writes zeros to dW.
  */
 #ifndef DFX_GEMM_H
 #define DFX_GEMM_H
@@ -111,6 +123,9 @@ int dfx_conv1x1_chain_f32(const float *W3, const float *X1, long strideX1, int K
 int dfx_gemm_wgrad_f32(const float *dY, long ldy, const float *X, long ldx,
                        float *dW, long ldw, float *db,
                        int M, int N, int K, int splits, float *workspace, void *stream);
+
+int dfx_conv1x1_wgrad_f32(const float *dZ, long strideZ, const float *X, long strideX, float *dW,
+                          int Co, int Ci, int HW, int batch, int splits, float *workspace, void *stream);
 
 #ifdef __cplusplus
 }
