@@ -28,7 +28,13 @@
 // shared between queries and is accumulated with hardware float atomics into a zero-filled buffer; when the
 // caller passes none (the memory is detached) the NEED_VALUE = false instantiation contains no atomic and no
 // corner store at all.
+//
+// Deterministic mode (fixed_sum.h): the accumulation of grad_value is a compile-time policy.  FloatSum is the route above;
+// FixedSum adds to_fixed(the same fp32 product) by return-less 64-bit integer atomics into a caller-owned, zero-filled
+// int64 [N,S,M,D] workspace - same lane map, the 8 lanes of a head add 256 contiguous bytes - which one streaming kernel
+// (fixed_sum.hip) converts to fp32 grad_value.  The three small gradients do not touch the policy and keep their bits.
 #include "dfx_common.h"
+#include "fixed_sum.h"
 #include "msda_tap.h"
 
 namespace {
@@ -36,23 +42,6 @@ namespace {
 using dfx::all_heads_sum;
 using dfx::head_sum;
 using dfx::xcd_remap;
-
-// One bilinear corner: its share of d out / d (h, w, weight) and, with NEED_VALUE, of grad_value.
-template <bool NEED_VALUE>
-__device__ __forceinline__ void corner(const float *__restrict__ vl, float *__restrict__ gl, int o, float wgt, float GH,
-                                       float GW, const float4 &t, float4 &gh, float4 &gw, float4 &val)
-{
-    const float4 v = *reinterpret_cast<const float4 *>(vl + o);
-    gh.x += GH * v.x; gh.y += GH * v.y; gh.z += GH * v.z; gh.w += GH * v.w;
-    gw.x += GW * v.x; gw.y += GW * v.y; gw.z += GW * v.z; gw.w += GW * v.w;
-    val.x += wgt * v.x; val.y += wgt * v.y; val.z += wgt * v.z; val.w += wgt * v.w;
-    if constexpr (NEED_VALUE) {
-        unsafeAtomicAdd(gl + o, wgt * t.x);
-        unsafeAtomicAdd(gl + o + 1, wgt * t.y);
-        unsafeAtomicAdd(gl + o + 2, wgt * t.z);
-        unsafeAtomicAdd(gl + o + 3, wgt * t.w);
-    }
-}
 
 // Filled by name in the entry point, passed by value.
 struct FusedBwdArgs {
@@ -62,9 +51,45 @@ struct FusedBwdArgs {
     float *grad_value, *grad_off, *grad_logits, *grad_ref;      // grad_value, grad_ref: may be null
     long off_stride, logit_stride, goff_stride, glog_stride;
     int NQ, Lq, S;
+    // FixedSum only (after the float route's fields, whose kernel-argument offsets stay): workspace, scale word, F
+    unsigned long long *fixed_ws;
+    const void *scratch;
+    int F;
 };
 
-template <int LT, int REFDIM, bool NEED_VALUE>
+// How a lane adds one fp32 product into grad_value: the element type of the buffer it adds into, that buffer, the add.
+// `up` is 2^(F-e) of fixed_sum.h and means nothing to the float route.
+struct FloatSum {
+    using type = float;
+    __device__ __forceinline__ static float *base(const FusedBwdArgs &g) { return g.grad_value; }
+    __device__ __forceinline__ static double scale(const FusedBwdArgs &) { return 0.; }
+    __device__ __forceinline__ static void add(float *p, float x, double) { unsafeAtomicAdd(p, x); }
+};
+struct FixedSum {
+    using type = unsigned long long;            // the int64 workspace, laid out like grad_value
+    __device__ __forceinline__ static type *base(const FusedBwdArgs &g) { return g.fixed_ws; }
+    __device__ __forceinline__ static double scale(const FusedBwdArgs &g) { return dfx::fixed::load_scale(g.scratch, g.F).up; }
+    __device__ __forceinline__ static void add(type *p, float x, double up) { atomicAdd(p, dfx::fixed::to_fixed(x, up)); }
+};
+
+// One bilinear corner: its share of d out / d (h, w, weight) and, with NEED_VALUE, of grad_value.
+template <bool NEED_VALUE, typename SUM>
+__device__ __forceinline__ void corner(const float *__restrict__ vl, typename SUM::type *__restrict__ gl, double up, int o,
+                                       float wgt, float GH, float GW, const float4 &t, float4 &gh, float4 &gw, float4 &val)
+{
+    const float4 v = *reinterpret_cast<const float4 *>(vl + o);
+    gh.x += GH * v.x; gh.y += GH * v.y; gh.z += GH * v.z; gh.w += GH * v.w;
+    gw.x += GW * v.x; gw.y += GW * v.y; gw.z += GW * v.z; gw.w += GW * v.w;
+    val.x += wgt * v.x; val.y += wgt * v.y; val.z += wgt * v.z; val.w += wgt * v.w;
+    if constexpr (NEED_VALUE) {
+        SUM::add(gl + o, wgt * t.x, up);
+        SUM::add(gl + o + 1, wgt * t.y, up);
+        SUM::add(gl + o + 2, wgt * t.z, up);
+        SUM::add(gl + o + 3, wgt * t.w, up);
+    }
+}
+
+template <int LT, int REFDIM, bool NEED_VALUE, typename SUM = FloatSum>
 __global__ __launch_bounds__(256) void msda_fused_bwd(const FusedBwdArgs g)
 {
     const int blk = xcd_remap(blockIdx.x, gridDim.x);
@@ -75,6 +100,8 @@ __global__ __launch_bounds__(256) void msda_fused_bwd(const FusedBwdArgs g)
     const int b = qi / g.Lq;
     const long chan = (long)b * g.S * 256 + m * 32 + cg * 4;
     const float4 top = *reinterpret_cast<const float4 *>(g.grad_out + (long)qi * 256 + lane * 4);
+
+    const double up = SUM::scale(g);
 
     // every level's size up front, as the taps kernels do: read per level between the stores and atomics of the loop
     // below they cost two VGPRs (the struct's pointers carry no __restrict__) and, at L = 2, a wave per SIMD
@@ -112,7 +139,7 @@ __global__ __launch_bounds__(256) void msda_fused_bwd(const FusedBwdArgs g)
         const int H = lv.H[l], W = lv.W[l];
         const long lvl = chan + (long)lv.R[l] * 256;
         const float *vl = g.value + lvl;
-        float *gl = NEED_VALUE ? g.grad_value + lvl : nullptr;
+        typename SUM::type *gl = NEED_VALUE ? SUM::base(g) + lvl : nullptr;
         const dfx::RefPoint r = dfx::load_ref<REFDIM>(g.ref + ((long)qi * LT + l) * REFDIM);
         const float4 *op = reinterpret_cast<const float4 *>(g.off + (long)qi * g.off_stride + (m * LT + l) * 8);
         const float4 o01 = op[0], o23 = op[1];
@@ -133,10 +160,10 @@ __global__ __launch_bounds__(256) void msda_fused_bwd(const FusedBwdArgs g)
                 const float lh = h_im - hf, lw = w_im - wf, hh = 1.f - lh, hw = 1.f - lw;
                 const float4 t = make_float4(top.x * weight, top.y * weight, top.z * weight, top.w * weight);
                 float4 gh = make_float4(0.f, 0.f, 0.f, 0.f), gw = gh, val = gh;
-                if (h0 >= 0 && w0 >= 0) corner<NEED_VALUE>(vl, gl, (h0 * W + w0) * 256, hh * hw, -hw, -hh, t, gh, gw, val);
-                if (h0 >= 0 && w1 <= W - 1) corner<NEED_VALUE>(vl, gl, (h0 * W + w1) * 256, hh * lw, -lw, hh, t, gh, gw, val);
-                if (h1 <= H - 1 && w0 >= 0) corner<NEED_VALUE>(vl, gl, (h1 * W + w0) * 256, lh * hw, hw, -lh, t, gh, gw, val);
-                if (h1 <= H - 1 && w1 <= W - 1) corner<NEED_VALUE>(vl, gl, (h1 * W + w1) * 256, lh * lw, lw, lh, t, gh, gw, val);
+                if (h0 >= 0 && w0 >= 0) corner<NEED_VALUE, SUM>(vl, gl, up, (h0 * W + w0) * 256, hh * hw, -hw, -hh, t, gh, gw, val);
+                if (h0 >= 0 && w1 <= W - 1) corner<NEED_VALUE, SUM>(vl, gl, up, (h0 * W + w1) * 256, hh * lw, -lw, hh, t, gh, gw, val);
+                if (h1 <= H - 1 && w0 >= 0) corner<NEED_VALUE, SUM>(vl, gl, up, (h1 * W + w0) * 256, lh * hw, hw, -lh, t, gh, gw, val);
+                if (h1 <= H - 1 && w1 <= W - 1) corner<NEED_VALUE, SUM>(vl, gl, up, (h1 * W + w1) * 256, lh * lw, lw, lh, t, gh, gw, val);
                 g_a = top.x * val.x + top.y * val.y + top.z * val.z + top.w * val.w;
                 s_w = gw.x * t.x + gw.y * t.y + gw.z * t.z + gw.w * t.w;
                 s_h = gh.x * t.x + gh.y * t.y + gh.z * t.z + gh.w * t.w;
@@ -189,27 +216,29 @@ __global__ __launch_bounds__(256) void msda_fused_bwd(const FusedBwdArgs g)
                             a[k * 4 + 2] * (ga[k * 4 + 2] - dot), a[k * 4 + 3] * (ga[k * 4 + 3] - dot));
 }
 
-template <int LT, int REFDIM, bool NEED_VALUE>
+template <int LT, int REFDIM, bool NEED_VALUE, typename SUM = FloatSum>
 int launch(const FusedBwdArgs &g, hipStream_t st)
 {
-    hipLaunchKernelGGL((msda_fused_bwd<LT, REFDIM, NEED_VALUE>), dim3((unsigned)((g.NQ + 3) / 4)), dim3(256), 0, st, g);
+    hipLaunchKernelGGL((msda_fused_bwd<LT, REFDIM, NEED_VALUE, SUM>), dim3((unsigned)((g.NQ + 3) / 4)), dim3(256), 0, st, g);
     return dfx::check_launch("msda_fused_bwd");
 }
 
-}  // namespace
-
-extern "C" int dfx_msda_fused_backward_f32(const float *value, const int64_t *shapes, const int64_t *lsi,
-                                           const float *ref, int ref_dim, const float *off, long off_stride,
-                                           const float *logits, long logit_stride, const float *grad_out, int N,
-                                           int S, int M, int D, int L, int Lq, int P, float *grad_value,
-                                           float *grad_off, long grad_off_stride, float *grad_logits,
-                                           long grad_logit_stride, float *grad_ref, void *stream)
+// Both entry points.  fixed_ws == nullptr: the float route (grad_value accumulated into, may be null).  Otherwise the
+// fixed-point route: grad_value is WRITTEN from the workspace's sums.
+int backward(const char *what, const float *value, const int64_t *shapes, const int64_t *lsi, const float *ref, int ref_dim,
+             const float *off, long off_stride, const float *logits, long logit_stride, const float *grad_out, int N, int S,
+             int M, int D, int L, int Lq, int P, float *grad_value, long long *fixed_ws, void *scratch, float *grad_off,
+             long grad_off_stride, float *grad_logits, long grad_logit_stride, float *grad_ref, hipStream_t st)
 {
-    const char *what = "msda fused backward";
     const int rc = dfx::check_fused(what, "dfx_msda_backward_f32", value, shapes, lsi, ref, ref_dim, off, off_stride, logits,
                                     logit_stride, grad_out, N, S, M, D, L, Lq, P);
     if (rc < 0) return rc;
-    if (rc == 1) return DFX_OK;
+    const long nvalue = (long)N * S * M * D;
+    if (rc == 1) {      // no query: nothing is added; the fixed route owes its caller the zeros it would have converted
+        if (fixed_ws && nvalue > 0 && hipMemsetAsync(grad_value, 0, sizeof(float) * nvalue, st) != hipSuccess)
+            return dfx::fail(DFX_ELAUNCH, "%s: memset failed", what);
+        return DFX_OK;
+    }
     if (!grad_off || !grad_logits) return dfx::fail(DFX_EINVAL, "%s: null gradient buffer", what);
     const long orow = (long)M * L * P * 2, lrow = (long)M * L * P;
     if (grad_off_stride < orow || grad_logit_stride < lrow || ((grad_off_stride | grad_logit_stride) & 3))
@@ -217,7 +246,6 @@ extern "C" int dfx_msda_fused_backward_f32(const float *value, const int64_t *sh
     if (!dfx::aligned16(grad_value) || !dfx::aligned16(grad_off) || !dfx::aligned16(grad_logits) || !dfx::aligned16(grad_ref))
         return dfx::fail(DFX_EINVAL, "%s: buffers must be 16-byte aligned", what);
     const long nq = (long)N * Lq;
-    hipStream_t st = static_cast<hipStream_t>(stream);
     if (S == 0) {
         if (hipMemset2DAsync(grad_off, sizeof(float) * grad_off_stride, 0, sizeof(float) * orow, nq, st) != hipSuccess ||
             hipMemset2DAsync(grad_logits, sizeof(float) * grad_logit_stride, 0, sizeof(float) * lrow, nq, st) != hipSuccess ||
@@ -230,8 +258,49 @@ extern "C" int dfx_msda_fused_backward_f32(const float *value, const int64_t *sh
     g.grad_value = grad_value; g.grad_off = grad_off; g.grad_logits = grad_logits; g.grad_ref = grad_ref;
     g.off_stride = off_stride; g.logit_stride = logit_stride; g.goff_stride = grad_off_stride; g.glog_stride = grad_logit_stride;
     g.NQ = (int)nq; g.Lq = Lq; g.S = S;
-    return dfx::dispatch_fused(L, ref_dim, [&](auto lt, auto rd) {
-        constexpr int LT = decltype(lt)::value, RD = decltype(rd)::value;
-        return grad_value ? launch<LT, RD, true>(g, st) : launch<LT, RD, false>(g, st);
+    if (!fixed_ws)
+        return dfx::dispatch_fused(L, ref_dim, [&](auto lt, auto rd) {
+            constexpr int LT = decltype(lt)::value, RD = decltype(rd)::value;
+            return grad_value ? launch<LT, RD, true>(g, st) : launch<LT, RD, false>(g, st);
+        });
+    g.fixed_ws = reinterpret_cast<unsigned long long *>(fixed_ws);
+    g.scratch = scratch;
+    g.F = dfx::fixed::fraction_bits(dfx::fixed::msda_terms(Lq));
+    if (const int e = dfx::fixed::enqueue_absmax(what, grad_out, nq * M * D, scratch, st)) return e;
+    const int e = dfx::dispatch_fused(L, ref_dim, [&](auto lt, auto rd) {
+        return launch<decltype(lt)::value, decltype(rd)::value, true, FixedSum>(g, st);
     });
+    return e ? e : dfx::fixed::enqueue_convert(what, fixed_ws, scratch, g.F, grad_value, nvalue, st);
+}
+
+}  // namespace
+
+extern "C" int dfx_msda_fused_backward_f32(const float *value, const int64_t *shapes, const int64_t *lsi,
+                                           const float *ref, int ref_dim, const float *off, long off_stride,
+                                           const float *logits, long logit_stride, const float *grad_out, int N,
+                                           int S, int M, int D, int L, int Lq, int P, float *grad_value,
+                                           float *grad_off, long grad_off_stride, float *grad_logits,
+                                           long grad_logit_stride, float *grad_ref, void *stream)
+{
+    return backward("msda fused backward", value, shapes, lsi, ref, ref_dim, off, off_stride, logits, logit_stride, grad_out, N,
+                    S, M, D, L, Lq, P, grad_value, nullptr, nullptr, grad_off, grad_off_stride, grad_logits, grad_logit_stride,
+                    grad_ref, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int dfx_msda_fused_backward_fixed_f32(const float *value, const int64_t *shapes, const int64_t *lsi,
+                                                 const float *ref, int ref_dim, const float *off, long off_stride,
+                                                 const float *logits, long logit_stride, const float *grad_out, int N,
+                                                 int S, int M, int D, int L, int Lq, int P, float *grad_value,
+                                                 long long *workspace, void *scratch, float *grad_off,
+                                                 long grad_off_stride, float *grad_logits, long grad_logit_stride,
+                                                 float *grad_ref, void *stream)
+{
+    const char *what = "msda fused backward (fixed)";
+    if (!grad_value || !workspace || !scratch)
+        return dfx::fail(DFX_EINVAL, "%s: null grad_value, workspace or scratch word (without a value gradient call "
+                                     "dfx_msda_fused_backward_f32 with grad_value == NULL)", what);
+    if (!dfx::aligned16(workspace) || !dfx::aligned16(scratch)) return dfx::fail(DFX_EINVAL, "%s: buffers must be 16-byte aligned", what);
+    return backward(what, value, shapes, lsi, ref, ref_dim, off, off_stride, logits, logit_stride, grad_out, N, S, M, D, L, Lq, P,
+                    grad_value, workspace, scratch, grad_off, grad_off_stride, grad_logits, grad_logit_stride, grad_ref,
+                    static_cast<hipStream_t>(stream));
 }

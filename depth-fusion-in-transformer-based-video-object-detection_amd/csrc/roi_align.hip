@@ -26,8 +26,12 @@
 //   roi_align_bwd_nchw  API parity with the NCHW forward: one thread per grad_out element, four scalar atomics per
 //     sample, i.e. 64 lanes in 64 different rows per wave instruction - an order of magnitude below the shaped
 //     form's atomic rate.  The model never takes it (frame_stage hands RoIAlign a channels-last view).
+// Not bit-reproducible in the default mode: the arrival order of the float atomics is not fixed.  The deterministic mode
+// (fixed_sum.h; dfx_roi_align_backward_nhwc_fixed_f32) instantiates the two NHWC kernels with FIXED = true: the same terms,
+// added as 64-bit integers into a workspace that one more kernel converts; sampling_ratio > 0 only, the NCHW form has no twin.
 #include "dfx_common.h"
 #include "dfx_roi.h"
+#include "fixed_sum.h"
 
 namespace {
 
@@ -157,10 +161,26 @@ struct AxisTaps {
     }
 };
 
-template <int SR>
+// Where the two NHWC backward kernels add (fixed_sum.h): FIXED = false is the float route, hardware fp32 atomics into
+// grad_input; FIXED = true adds to_fixed(the same fp32 product) by return-less 64-bit integer atomics into an int64
+// workspace laid out like grad_input, which fixed_sum.hip's convert kernel turns into grad_input.
+struct FixedTarget {
+    unsigned long long *ws;
+    const void *scratch;
+    int F;
+};
+
+template <bool FIXED>
+__device__ __forceinline__ void roi_add(float *p, unsigned long long *wp, float x, double up)
+{
+    if constexpr (FIXED) atomicAdd(wp, dfx::fixed::to_fixed(x, up));
+    else unsafeAtomicAdd(p, x);
+}
+
+template <int SR, bool FIXED = false>
 __global__ __launch_bounds__(256) void roi_align_bwd_nhwc(const float *__restrict__ gout, const float *__restrict__ rois,
                                                           int N, int C, int H, int W, long nbins, int ph, int pw,
-                                                          float scale, int aligned, float *__restrict__ gin)
+                                                          float scale, int aligned, float *__restrict__ gin, const FixedTarget fx)
 {
     const long bin = (long)blockIdx.x * 4 + (threadIdx.x >> 6);     // one wave per (roi, bin)
     if (bin >= nbins) return;
@@ -182,6 +202,8 @@ __global__ __launch_bounds__(256) void roi_align_bwd_nhwc(const float *__restric
     if (ty.n == 0 || tx.n == 0) return;
     const float inv = 1.f / (float)(SR * SR);
     float *dst = gin + (long)r.b * H * W * C;
+    unsigned long long *wdst = FIXED ? fx.ws + (long)r.b * H * W * C : nullptr;
+    const double up = FIXED ? dfx::fixed::load_scale(fx.scratch, fx.F).up : 0.;
     const float *g = gout + bin * C;
     for (int c = lane; c < C; c += 64) {
         const float gv = g[c] * inv;
@@ -191,15 +213,18 @@ __global__ __launch_bounds__(256) void roi_align_bwd_nhwc(const float *__restric
 #pragma unroll
             for (int b = 0; b < 2 * SR; ++b) {
                 if (b >= tx.n) break;
-                unsafeAtomicAdd(dst + ((long)ty.idx[a] * W + tx.idx[b]) * C + c, ty.w[a] * tx.w[b] * gv);
+                roi_add<FIXED>(dst + ((long)ty.idx[a] * W + tx.idx[b]) * C + c, wdst + ((long)ty.idx[a] * W + tx.idx[b]) * C + c,
+                               ty.w[a] * tx.w[b] * gv, up);
             }
         }
     }
 }
 
+template <bool FIXED = false>
 __global__ __launch_bounds__(256) void roi_align_bwd_nhwc_plain(const float *__restrict__ gout, const float *__restrict__ rois,
                                                                 int N, int C, int H, int W, long nbins, int ph, int pw,
-                                                                float scale, int sr, int aligned, float *__restrict__ gin)
+                                                                float scale, int sr, int aligned, float *__restrict__ gin,
+                                                                const FixedTarget fx)
 {
     const long bin = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (bin >= nbins) return;
@@ -210,6 +235,8 @@ __global__ __launch_bounds__(256) void roi_align_bwd_nhwc_plain(const float *__r
     if (r.b < 0 || r.b >= N) return;
     const float inv = 1.f / (float)(sr * sr);
     float *dst = gin + (long)r.b * H * W * C;
+    unsigned long long *wdst = FIXED ? fx.ws + (long)r.b * H * W * C : nullptr;
+    const double up = FIXED ? dfx::fixed::load_scale(fx.scratch, fx.F).up : 0.;
     const float *g = gout + bin * C;
     for (int c = lane; c < C; c += 64) {
         const float gv = g[c] * inv;
@@ -219,10 +246,10 @@ __global__ __launch_bounds__(256) void roi_align_bwd_nhwc_plain(const float *__r
                 const float x = r.x1 + j * r.bin_w + (ix + 0.5f) * r.bin_w / (float)sr;
                 const Sample s = locate(y, x, H, W);
                 if (!s.ok) continue;
-                unsafeAtomicAdd(dst + ((long)s.yl * W + s.xl) * C + c, s.w1 * gv);
-                unsafeAtomicAdd(dst + ((long)s.yl * W + s.xh) * C + c, s.w2 * gv);
-                unsafeAtomicAdd(dst + ((long)s.yh * W + s.xl) * C + c, s.w3 * gv);
-                unsafeAtomicAdd(dst + ((long)s.yh * W + s.xh) * C + c, s.w4 * gv);
+                roi_add<FIXED>(dst + ((long)s.yl * W + s.xl) * C + c, wdst + ((long)s.yl * W + s.xl) * C + c, s.w1 * gv, up);
+                roi_add<FIXED>(dst + ((long)s.yl * W + s.xh) * C + c, wdst + ((long)s.yl * W + s.xh) * C + c, s.w2 * gv, up);
+                roi_add<FIXED>(dst + ((long)s.yh * W + s.xl) * C + c, wdst + ((long)s.yh * W + s.xl) * C + c, s.w3 * gv, up);
+                roi_add<FIXED>(dst + ((long)s.yh * W + s.xh) * C + c, wdst + ((long)s.yh * W + s.xh) * C + c, s.w4 * gv, up);
             }
         }
     }
@@ -312,6 +339,31 @@ int begin_backward(const float *grad_out, const float *rois, float *grad_input, 
     return K == 0 ? 1 : 0;
 }
 
+// the merged kernel of the sampling ratio, or the plain one (sampling_ratio > 4, DFX_ROI_BWD_PLAIN), adding by policy FIXED
+template <bool FIXED>
+int launch_backward_nhwc(const float *grad_out, const float *rois, int N, int C, int H, int W, int K, int ph, int pw,
+                         float spatial_scale, int sampling_ratio, int aligned, float *grad_input, const FixedTarget fx,
+                         hipStream_t st)
+{
+    const long nbins = (long)K * ph * pw;
+    const dim3 grid((unsigned)((nbins + 3) / 4)), block(256);
+    const int sr = dfx::tuning().roi_bwd_plain ? 0 : sampling_ratio;
+#define DFX_ROI_BWD(SR)                                                                                                \
+    hipLaunchKernelGGL((roi_align_bwd_nhwc<SR, FIXED>), grid, block, 0, st, grad_out, rois, N, C, H, W, nbins, ph, pw,   \
+                       spatial_scale, aligned, grad_input, fx)
+    switch (sr) {
+    case 1: DFX_ROI_BWD(1); break;
+    case 2: DFX_ROI_BWD(2); break;
+    case 3: DFX_ROI_BWD(3); break;
+    case 4: DFX_ROI_BWD(4); break;
+    default:
+        hipLaunchKernelGGL(roi_align_bwd_nhwc_plain<FIXED>, grid, block, 0, st, grad_out, rois, N, C, H, W, nbins, ph, pw,
+                           spatial_scale, sampling_ratio, aligned, grad_input, fx);
+    }
+#undef DFX_ROI_BWD
+    return dfx::check_launch("roi_align_bwd_nhwc");
+}
+
 }  // namespace
 
 extern "C" int dfx_roi_align_backward_nhwc_f32(const float *grad_out, const float *rois, int N, int C, int H, int W, int K,
@@ -322,23 +374,32 @@ extern "C" int dfx_roi_align_backward_nhwc_f32(const float *grad_out, const floa
     const int rc = begin_backward(grad_out, rois, grad_input, N, C, H, W, K, ph, pw, sampling_ratio, true, st);
     if (rc < 0) return rc;
     if (rc == 1) return DFX_OK;
-    const long nbins = (long)K * ph * pw;
-    const dim3 grid((unsigned)((nbins + 3) / 4)), block(256);
-    const int sr = dfx::tuning().roi_bwd_plain ? 0 : sampling_ratio;
-#define DFX_ROI_BWD(SR)                                                                                                \
-    hipLaunchKernelGGL(roi_align_bwd_nhwc<SR>, grid, block, 0, st, grad_out, rois, N, C, H, W, nbins, ph, pw, spatial_scale, \
-                       aligned, grad_input)
-    switch (sr) {
-    case 1: DFX_ROI_BWD(1); break;
-    case 2: DFX_ROI_BWD(2); break;
-    case 3: DFX_ROI_BWD(3); break;
-    case 4: DFX_ROI_BWD(4); break;
-    default:
-        hipLaunchKernelGGL(roi_align_bwd_nhwc_plain, grid, block, 0, st, grad_out, rois, N, C, H, W, nbins, ph, pw,
-                           spatial_scale, sampling_ratio, aligned, grad_input);
-    }
-#undef DFX_ROI_BWD
-    return dfx::check_launch("roi_align_bwd_nhwc");
+    return launch_backward_nhwc<false>(grad_out, rois, N, C, H, W, K, ph, pw, spatial_scale, sampling_ratio, aligned, grad_input,
+                                       FixedTarget{}, st);
+}
+
+extern "C" int dfx_roi_align_backward_nhwc_fixed_f32(const float *grad_out, const float *rois, int N, int C, int H, int W,
+                                                     int K, int ph, int pw, float spatial_scale, int sampling_ratio,
+                                                     int aligned, float *grad_input, long long *workspace, void *scratch,
+                                                     void *stream)
+{
+    const char *what = "roi_align_backward nhwc (fixed)";
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (!workspace || !scratch || !dfx::aligned16(workspace) || !dfx::aligned16(scratch))
+        return dfx::fail(DFX_EINVAL, "%s: null or misaligned workspace or scratch word", what);
+    if (ph > 0 && pw > 0 && sampling_ratio > 0 && dfx::fixed::roi_terms(K, ph, pw, sampling_ratio) >= dfx::fixed::MAX_TERMS)
+        return dfx::fail(DFX_ERANGE, "%s: too many contributions per pixel for the fixed-point sum", what);
+    // the float entry's checks; its zero fill gives the K == 0 answer, and is overwritten by the convert otherwise
+    const int rc = begin_backward(grad_out, rois, grad_input, N, C, H, W, K, ph, pw, sampling_ratio, true, st);
+    if (rc < 0) return rc;
+    if (rc == 1) return DFX_OK;
+    const FixedTarget fx{reinterpret_cast<unsigned long long *>(workspace), scratch,
+                         dfx::fixed::fraction_bits(dfx::fixed::roi_terms(K, ph, pw, sampling_ratio))};
+    if (const int e = dfx::fixed::enqueue_absmax(what, grad_out, (long)K * ph * pw * C, scratch, st)) return e;
+    if (const int e = launch_backward_nhwc<true>(grad_out, rois, N, C, H, W, K, ph, pw, spatial_scale, sampling_ratio, aligned,
+                                                 grad_input, fx, st))
+        return e;
+    return dfx::fixed::enqueue_convert(what, workspace, scratch, fx.F, grad_input, (long)N * C * H * W, st);
 }
 
 extern "C" int dfx_roi_align_backward_nchw_f32(const float *grad_out, const float *rois, int N, int C, int H, int W, int K,

@@ -28,6 +28,13 @@ SIGNATURES = {
     "dfx_msda_fused_backward_f32": [_p, _p, _p, _p, _i, _p, _l, _p, _l, _p] + _DIMS + [_p, _p, _l, _p, _l, _p, _p],
     # ref, ref_dim, off, off_pitch, logits, logit_pitch, grad_out, N, H, W, Lq, grad_value, stream (csrc/msda_level_backward.hip)
     "dfx_msda_level_grad_value_f32": [_p, _i, _p, _l, _p, _l, _p, _i, _i, _i, _i, _p, _p],
+    # the deterministic twins (csrc/fixed_sum.h): ... grad_value, [int64 workspace,] 16-byte scratch word, ...
+    "dfx_msda_fixed_fraction_bits": [_i],
+    "dfx_msda_level_grad_value_fixed_f32": [_p, _i, _p, _l, _p, _l, _p, _i, _i, _i, _i, _p, _p, _p],
+    "dfx_msda_fused_backward_fixed_f32": [_p, _p, _p, _p, _i, _p, _l, _p, _l, _p] + _DIMS + [_p, _p, _p, _p, _l, _p, _l, _p, _p],
+    # K, ph, pw, sampling_ratio;  the float entry's arguments + int64 workspace, scratch word, stream
+    "dfx_roi_align_fixed_fraction_bits": [_i, _i, _i, _i],
+    "dfx_roi_align_backward_nhwc_fixed_f32": [_p, _p] + [_i] * 7 + [ctypes.c_float, _i, _i, _p, _p, _p, _p],
     "dfx_profile_enable": [_i],
     "dfx_tuning_reload": [],
     "dfx_profile_drain": [_p, _p, _p, _p, _i],

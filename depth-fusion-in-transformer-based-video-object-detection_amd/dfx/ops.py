@@ -7,6 +7,7 @@ sampling_loc.size(1), P from sampling_loc.size(4)), fresh output tensors.
 """
 import ctypes
 import os
+import warnings
 
 import torch
 
@@ -29,6 +30,11 @@ LEVEL_MIN_QUERIES = 1024
 # at 4 / 32 frames x 4200; at 4 x 300 = 1200 the two routes tie inside a 20-35 % spread, and nothing between was measured.
 USE_LEVEL_BWD = os.environ.get("DFX_MSDA_LEVEL_BWD", "1") != "0"
 LEVEL_BWD_MIN_QUERIES = 9600
+# Deterministic mode: the gradients many queries / RoIs add into - grad_value of the fused MSDA backward,
+# grad_input of the channels-last RoIAlign - are summed in 64-bit fixed point (csrc/fixed_sum.h), bit-identical from call
+# to call and under any order of the queries / RoIs.  On with torch.use_deterministic_algorithms(True); DFX_DETERMINISTIC=0
+# opts this library out (A/B runs), DFX_DETERMINISTIC=1 turns the mode on without the torch flag.  Read once, at import.
+_DETERMINISTIC_ENV = os.environ.get("DFX_DETERMINISTIC")
 # convolutions of <= 4 input channels from an LDS-resident input tile (csrc/conv_tile.hip); 0: on the implicit GEMM (A/B runs)
 USE_TILE_CONV = os.environ.get("DFX_TILE_CONV", "1") == "1"
 
@@ -60,6 +66,33 @@ def profile_stop(cap=65536):
 def _require(cond, msg):
     if not cond:
         raise RuntimeError(msg)
+
+
+def deterministic_mode():
+    """True when the backward routes must give the same bits on every call: torch's flag, unless DFX_DETERMINISTIC says
+    otherwise.  The autograd nodes ask at backward time, as torch's own operators do."""
+    if _DETERMINISTIC_ENV == "0":
+        return False
+    return _DETERMINISTIC_ENV == "1" or torch.are_deterministic_algorithms_enabled()
+
+
+_ALERTED = set()       # operations that have warned under warn_only (once each)
+
+
+def _alert_not_deterministic(op, deterministic=None):
+    """What a torch operator without a deterministic implementation does, for the routes without a fixed-point twin:
+    under the mode (`deterministic` None: ask it) raise RuntimeError naming `op`, or - when torch is set to warn only -
+    warn once per operation and let the caller run as it does today.  Outside the mode nothing happens."""
+    if not (deterministic_mode() if deterministic is None else deterministic):
+        return
+    msg = (f"{op} does not have a deterministic implementation, but the deterministic mode is on "
+           "(torch.use_deterministic_algorithms(True) or DFX_DETERMINISTIC=1).  Turn the mode off for this operation "
+           "(DFX_DETERMINISTIC=0 for this library alone) or pass warn_only=True to torch.use_deterministic_algorithms.")
+    if not torch.is_deterministic_algorithms_warn_only_enabled():
+        raise RuntimeError(msg)
+    if op not in _ALERTED:
+        _ALERTED.add(op)
+        warnings.warn(msg, UserWarning, stacklevel=3)
 
 
 def _check_inputs(named):
@@ -166,6 +199,8 @@ def msda_forward(value, spatial_shapes, level_start_index, sampling_loc, attn_we
 
 def msda_backward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output,
                   im2col_step=64):
+    # float atomics for every dtype; the reference's C signature has no room for a workspace
+    _alert_not_deterministic("ms_deform_attn_backward")
     _check_inputs([("value", value), ("spatial_shapes", spatial_shapes),
                    ("level_start_index", level_start_index), ("sampling_loc", sampling_loc),
                    ("attn_weight", attn_weight), ("grad_output", grad_output)])
@@ -285,7 +320,7 @@ def _msda_fused_forward_split(value, spatial_shapes, level_start_index, referenc
 
 
 def msda_fused_backward(grad_out, value, spatial_shapes, level_start_index, reference_points, offsets, logits,
-                        need_value=True, need_ref=False):
+                        need_value=True, need_ref=False, deterministic=None):
     """Gradients of msda_fused from its inputs alone (include/dfx_msda.h, dfx_msda_fused_backward_f32: the kernel
     recomputes the softmax weights and the locations).  grad_out [N,Lq,M*D]; reference_points contiguous; offsets /
     logits as for msda_fused (rows may be column slices of a wider buffer).
@@ -293,7 +328,11 @@ def msda_fused_backward(grad_out, value, spatial_shapes, level_start_index, refe
     grad_value is summed with float atomics - global ones into a zero-filled buffer, or, for a single level that
     level_backward_supported admits, LDS ones in a second launch (dfx_msda_level_grad_value_f32) - and is only computed
     (and its buffer only allocated) with need_value; the other three are plain stores: two calls on the same inputs give
-    the same bits."""
+    the same bits.  deterministic (None: deterministic_mode()): the same routing rule with each side's fixed-point twin
+    (dfx_msda_fused_backward_fixed_f32 / dfx_msda_level_grad_value_fixed_f32, csrc/fixed_sum.h) - grad_value too is then
+    bit-identical from call to call and under any order of the queries; the other three keep their bits."""
+    # (an empty value map has no workspace to hand over and nothing to sum: the float entry answers it)
+    fixed = need_value and value.numel() > 0 and (deterministic_mode() if deterministic is None else bool(deterministic))
     N, S, M, D, L, Lq, P, _, ref_dim = _msda_fused_operands(
         "msda_fused_backward", value, spatial_shapes, level_start_index, reference_points,
         (("offsets", offsets, 2), ("logits", logits, 1)))
@@ -312,20 +351,35 @@ def msda_fused_backward(grad_out, value, spatial_shapes, level_start_index, refe
         _require(hw[0] * hw[1] == S, "msda_fused_backward: the level's H * W differs from the value map's token count")
         grad_value = torch.empty_like(value)
     else:
-        grad_value = torch.zeros_like(value) if need_value else None        # the one buffer the kernel accumulates into
+        # the one buffer the float kernel accumulates into (the fixed-point form allocates its own below)
+        grad_value = torch.zeros_like(value) if need_value and not fixed else None
     grad_off = torch.empty((N, Lq, M * L * P * 2), dtype=torch.float32, device=dev)
     grad_logits = torch.empty((N, Lq, M * L * P), dtype=torch.float32, device=dev)
     grad_ref = torch.empty((N, Lq, L, ref_dim), dtype=torch.float32, device=dev) if need_ref else None
-    _call("msda_fused_backward", "dfx_msda_fused_backward_f32", dev,
-          value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(), reference_points.data_ptr(), ref_dim,
-          offsets.data_ptr(), off_pitch, logits.data_ptr(), logit_pitch, grad_out.data_ptr(),
-          N, S, M, D, L, Lq, P, None if hw is not None else _ptr(grad_value), grad_off.data_ptr(), M * L * P * 2,
-          grad_logits.data_ptr(), M * L * P, _ptr(grad_ref))
+    front = (value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(), reference_points.data_ptr(), ref_dim,
+             offsets.data_ptr(), off_pitch, logits.data_ptr(), logit_pitch, grad_out.data_ptr(), N, S, M, D, L, Lq, P)
+    small = (grad_off.data_ptr(), M * L * P * 2, grad_logits.data_ptr(), M * L * P, _ptr(grad_ref))
+    if fixed and hw is None:
+        # the global form: int64 sums in a zero-filled workspace, which the entry converts into grad_value (written in full)
+        grad_value = torch.empty_like(value)
+        workspace = torch.zeros(value.shape, dtype=torch.int64, device=dev)
+        _call("msda_fused_backward", "dfx_msda_fused_backward_fixed_f32", dev, *front, grad_value.data_ptr(),
+              workspace.data_ptr(), _fixed_scratch(dev).data_ptr(), *small)
+        return grad_value, grad_off, grad_logits, grad_ref
+    _call("msda_fused_backward", "dfx_msda_fused_backward_f32", dev, *front, None if hw is not None else _ptr(grad_value), *small)
     if hw is not None:
-        _call("msda_fused_backward", "dfx_msda_level_grad_value_f32", dev,
-              reference_points.data_ptr(), ref_dim, offsets.data_ptr(), off_pitch, logits.data_ptr(), logit_pitch,
-              grad_out.data_ptr(), N, hw[0], hw[1], Lq, grad_value.data_ptr())
+        level = (reference_points.data_ptr(), ref_dim, offsets.data_ptr(), off_pitch, logits.data_ptr(), logit_pitch,
+                 grad_out.data_ptr(), N, hw[0], hw[1], Lq, grad_value.data_ptr())
+        if fixed:
+            _call("msda_fused_backward", "dfx_msda_level_grad_value_fixed_f32", dev, *level, _fixed_scratch(dev).data_ptr())
+        else:
+            _call("msda_fused_backward", "dfx_msda_level_grad_value_f32", dev, *level)
     return grad_value, grad_off, grad_logits, grad_ref
+
+
+def _fixed_scratch(dev):
+    """The 16-byte scale word of a fixed-point launch (csrc/fixed_sum.h): fresh per call, cleared and filled on the device."""
+    return torch.empty(4, dtype=torch.int32, device=dev)
 
 
 def level_backward_supported(L, H, W, N, Lq, M=8, D=32, P=4):
@@ -348,12 +402,13 @@ def _level_backward_size(spatial_shapes, M, D, L, P, N, Lq):
     return (H, W) if level_backward_supported(L, H, W, N, Lq, M, D, P) else None
 
 
-def msda_level_grad_value(grad_out, reference_points, offsets, logits, N, H, W):
+def msda_level_grad_value(grad_out, reference_points, offsets, logits, N, H, W, deterministic=None):
     """grad_value of single-level fused MSDA summed in LDS (include/dfx_msda.h, dfx_msda_level_grad_value_f32), on the
     operands of msda_fused_backward with one level.  A level that does not fit the CU's LDS raises; no other kernel steps in.
 
     grad_out [N,Lq,256], reference_points [N,Lq,1,2|4], offsets [N,Lq,64], logits [N,Lq,32] (rows may be column slices of
-    a wider buffer), all fp32 on one GPU  -> [N,H*W,8,32], every element written; last bits may differ between calls."""
+    a wider buffer), all fp32 on one GPU  -> [N,H*W,8,32], every element written; last bits may differ between calls,
+    unless deterministic (None: deterministic_mode()) selects dfx_msda_level_grad_value_fixed_f32 (csrc/fixed_sum.h)."""
     what = "msda_level_grad_value"
     reference_points = _level_reference_points(reference_points, N)
     Lq, ref_dim = reference_points.shape[1], reference_points.shape[3]
@@ -375,9 +430,11 @@ def msda_level_grad_value(grad_out, reference_points, offsets, logits, N, H, W):
     offsets, off_pitch = _pitched_rows(offsets, N, Lq, 64)
     logits, logit_pitch = _pitched_rows(logits, N, Lq, 32)
     grad_value = torch.empty((N, H * W, 8, 32), dtype=torch.float32, device=grad_out.device)
-    _call(what, "dfx_msda_level_grad_value_f32", grad_out.device,
+    fixed = deterministic_mode() if deterministic is None else bool(deterministic)
+    _call(what, "dfx_msda_level_grad_value_fixed_f32" if fixed else "dfx_msda_level_grad_value_f32", grad_out.device,
           reference_points.data_ptr(), ref_dim, offsets.data_ptr(), off_pitch, logits.data_ptr(), logit_pitch,
-          grad_out.data_ptr(), N, int(H), int(W), Lq, grad_value.data_ptr())
+          grad_out.data_ptr(), N, int(H), int(W), Lq, grad_value.data_ptr(),
+          *((_fixed_scratch(grad_out.device).data_ptr(),) if fixed else ()))
     return grad_value
 
 
@@ -394,6 +451,7 @@ class _MSDAFusedFunction(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_output):
         need = ctx.needs_input_grad
+        # (deterministic=None: msda_fused_backward asks deterministic_mode() now, at backward time, as torch's operators do)
         gv, go, gl, gr = msda_fused_backward(grad_output, *ctx.saved_tensors, need_value=need[0], need_ref=need[3])
         return gv, None, None, gr, go if need[4] else None, gl if need[5] else None
 
@@ -506,13 +564,24 @@ def _roi_align_forward(inp, rois, output_size, spatial_scale, sampling_ratio, al
 
 
 def roi_align_backward(grad_out, rois, input_shape, output_size, spatial_scale, sampling_ratio, aligned=True,
-                       channels_last=False):
+                       channels_last=False, deterministic=None):
     """Gradient of roi_align with respect to its input (the RoIs get none) through include/dfx_roi.h.
 
     channels_last=False: grad_out [K,C,ph,pw] contiguous -> [N,C,H,W] = input_shape
     channels_last=True : grad_out [K,ph*pw,C] contiguous -> [N,H,W,C] = input_shape
     The library zero-fills the fresh result and accumulates into it with fp32 atomics.
+    deterministic (None: deterministic_mode()): the channels-last form sums in 64-bit fixed point instead
+    (dfx_roi_align_backward_nhwc_fixed_f32, csrc/fixed_sum.h) - the same bits on every call and for any order of the RoIs.
+    The NCHW form and the adaptive grid (sampling_ratio <= 0) have no such twin: under the mode they raise, or warn once
+    and run as above when torch is set to warn only.
     """
+    fixed = deterministic_mode() if deterministic is None else bool(deterministic)
+    if fixed and not channels_last:
+        _alert_not_deterministic("roi_align_backward (NCHW)", True)
+        fixed = False
+    elif fixed and int(sampling_ratio) <= 0:
+        _alert_not_deterministic("roi_align_backward (adaptive sampling_ratio)", True)
+        fixed = False
     ph, pw = (output_size, output_size) if isinstance(output_size, int) else output_size
     rois = rois.contiguous().float()
     _check_inputs([("grad_output", grad_out), ("rois", rois)])
@@ -528,8 +597,13 @@ def roi_align_backward(grad_out, rois, input_shape, output_size, spatial_scale, 
         want, fn = (K, C, ph, pw), "dfx_roi_align_backward_nchw_f32"
     _require(tuple(grad_out.shape) == want, f"grad_output must be {want}, got {tuple(grad_out.shape)}")
     grad_input = torch.empty(tuple(input_shape), dtype=grad_out.dtype, device=grad_out.device)
+    extra = ()
+    if fixed:
+        fn = "dfx_roi_align_backward_nhwc_fixed_f32"
+        workspace = torch.zeros(tuple(input_shape), dtype=torch.int64, device=grad_out.device)
+        extra = (workspace.data_ptr(), _fixed_scratch(grad_out.device).data_ptr())
     _call("roi_align_backward", fn, grad_out.device, grad_out.data_ptr(), rois.data_ptr(), N, C, H, W, K, ph, pw,
-          float(spatial_scale), int(sampling_ratio), int(bool(aligned)), grad_input.data_ptr())
+          float(spatial_scale), int(sampling_ratio), int(bool(aligned)), grad_input.data_ptr(), *extra)
     return grad_input
 
 
@@ -547,6 +621,7 @@ class _RoIAlignFunction(torch.autograd.Function):
     def backward(ctx, grad_output):
         rois, = ctx.saved_tensors
         shape, output_size, spatial_scale, sampling_ratio, aligned, channels_last = ctx.args
+        # (the mode is asked inside, at backward time)
         grad_input = roi_align_backward(grad_output.contiguous(), rois, shape, output_size, spatial_scale, sampling_ratio,
                                         aligned, channels_last)
         return grad_input, None, None, None, None, None, None

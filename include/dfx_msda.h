@@ -238,8 +238,9 @@ int dfx_msda_fused_level_forward_f32(const float *value, const float *ref, int r
  *              included): the caller need not initialise it.
  * All argument checks run before any launch.  N == 0 returns DFX_OK without a launch; Lq == 0 with N > 0 writes zeros
  * to grad_value.  N*Lq < 2^28.  The softmax and the sampling locations are the level forward's arithmetic.
- * NOT bit-reproducible: the order of the LDS float adds is not fixed, so two calls may differ in the last bits - as
- * the global-atomic grad_value of dfx_msda_fused_backward_f32.  An addition to the ABI: dfx_abi_version() stays.
+ * NOT bit-reproducible in the default mode: the order of the LDS float adds is not fixed, so two calls may differ in the
+ * last bits - as the global-atomic grad_value of dfx_msda_fused_backward_f32; the _fixed_ entry points below are.
+ * An addition to the ABI: dfx_abi_version() stays.
  */
 int dfx_msda_level_grad_value_f32(const float *ref, int ref_dim,
                                   const float *off, long off_pitch,
@@ -247,6 +248,43 @@ int dfx_msda_level_grad_value_f32(const float *ref, int ref_dim,
                                   const float *grad_out,
                                   int N, int H, int W, int Lq,
                                   float *grad_value, void *stream);
+
+/*
+ * Deterministic grad_value (csrc/fixed_sum.h): the two entry points above with every contribution - the float route's
+ * own fp32 product - scaled by a power of two taken from max |grad_out| of the launch, rounded to a 64-bit integer and
+ * summed with integer atomics.  Integer addition is associative: grad_value has the same bits from call to call and
+ * under any permutation of the queries.  Scaling grad_out by a power of two scales grad_value by it exactly.
+ *   scratch     16 bytes, 16-byte aligned, caller-owned; the entry point clears it and leaves the bit pattern of
+ *               max |grad_out| in its first word.  The host never reads it.
+ *   workspace   (the fused form) N*S*M*D 64-bit integers laid out like grad_value, 16-byte aligned, ZERO-FILLED by the
+ *               caller; holds the sums after the call.
+ *   grad_value  WRITTEN in full by both forms (the caller need not initialise it); the fused form requires it - for the
+ *               three small gradients alone call dfx_msda_fused_backward_f32 with grad_value == NULL, which has no atomics.
+ * grad_off, grad_logits and grad_ref of the fused form are the bits of dfx_msda_fused_backward_f32.
+ * max |grad_out| == 0, Lq == 0: exact zeros.  ANY inf or NaN in grad_out makes EVERY element of grad_value NaN.
+ * dfx_msda_fixed_fraction_bits(Lq): the fraction bits F = min(50, 61 - ceil(log2(16 * Lq))) both forms use (16 * Lq
+ * bounds the (query, point, corner) triples that can meet in one element).
+ * Otherwise the argument rules, checks (all before any launch) and geometry of the float entry points.
+ * Additions to the ABI: dfx_abi_version() stays.
+ */
+int dfx_msda_fixed_fraction_bits(int Lq);
+int dfx_msda_level_grad_value_fixed_f32(const float *ref, int ref_dim,
+                                        const float *off, long off_pitch,
+                                        const float *logits, long logit_pitch,
+                                        const float *grad_out,
+                                        int N, int H, int W, int Lq,
+                                        float *grad_value, void *scratch, void *stream);
+int dfx_msda_fused_backward_fixed_f32(const float *value, const int64_t *shapes, const int64_t *lsi,
+                                      const float *ref, int ref_dim,
+                                      const float *off, long off_stride,
+                                      const float *logits, long logit_stride,
+                                      const float *grad_out,
+                                      int N, int S, int M, int D, int L, int Lq, int P,
+                                      float *grad_value, long long *workspace, void *scratch,
+                                      float *grad_off, long grad_off_stride,
+                                      float *grad_logits, long grad_logit_stride,
+                                      float *grad_ref,
+                                      void *stream);
 
 #ifdef __cplusplus
 }

@@ -34,7 +34,7 @@ int dfx_roi_align_nhwc_f32(const float *input, const float *rois, int N, int C, 
  * no gradient, as in the published mmcv op).  grad_out has the forward's output layout, grad_input the forward's
  * input layout.  Unlike dfx_msda_backward_* the entry point zero-fills grad_input [N*C*H*W floats] itself on
  * `stream` before it accumulates into it with fp32 atomic adds (also when K == 0, where it then returns), so
- * sums may differ in the last bits from run to run.  Samples the forward skips, and RoIs whose batch index is
+ * in the default mode sums may differ in the last bits from run to run.  Samples the forward skips, and RoIs whose batch index is
  * outside [0, N), contribute nothing.  Same argument rules as the forward; nhwc: C a multiple of 4, grad_out and
  * grad_input 16-byte aligned.  Additions to the ABI: no existing signature changes, dfx_abi_version() stays. */
 int dfx_roi_align_backward_nchw_f32(const float *grad_out, const float *rois, int N, int C, int H, int W, int K,
@@ -44,6 +44,21 @@ int dfx_roi_align_backward_nchw_f32(const float *grad_out, const float *rois, in
 int dfx_roi_align_backward_nhwc_f32(const float *grad_out, const float *rois, int N, int C, int H, int W, int K,
                                     int ph, int pw, float spatial_scale, int sampling_ratio, int aligned,
                                     float *grad_input, void *stream);
+
+/* Deterministic NHWC backward (csrc/fixed_sum.h): dfx_roi_align_backward_nhwc_f32 with every contribution - the float
+ * route's own fp32 product - scaled by a power of two taken from max |grad_out|, rounded to a 64-bit integer and summed
+ * with integer atomics, so grad_input has the same bits from call to call and under any permutation of the RoIs.
+ *   workspace  N*H*W*C 64-bit integers laid out like grad_input, 16-byte aligned, ZERO-FILLED by the caller
+ *   scratch    16 bytes, 16-byte aligned, caller-owned; cleared by the call, then holds the bit pattern of max |grad_out|
+ * grad_input is written in full.  max |grad_out| == 0 or K == 0: exact zeros; ANY inf or NaN in grad_out makes EVERY
+ * element NaN.  dfx_roi_align_fixed_fraction_bits: F = min(50, 61 - ceil(log2(4 * sr^2 * ph * pw * K))), the bound being
+ * the (RoI, bin, sample, corner) terms that can meet in one pixel; a launch whose bound reaches 2^32 is refused.
+ * The adaptive grid (sampling_ratio <= 0) has no host bound and is refused like everywhere on this path.
+ * Additions to the ABI: dfx_abi_version() stays. */
+int dfx_roi_align_fixed_fraction_bits(int K, int ph, int pw, int sampling_ratio);
+int dfx_roi_align_backward_nhwc_fixed_f32(const float *grad_out, const float *rois, int N, int C, int H, int W, int K,
+                                          int ph, int pw, float spatial_scale, int sampling_ratio, int aligned,
+                                          float *grad_input, long long *workspace, void *scratch, void *stream);
 
 /* DynamicConv of the query/RoI fusion head (Sparse R-CNN instance interaction) between the parameter
  * Linear and the output Linear, one launch (/root/reference/models/sparse_roi_head/head.py:98-113):

@@ -15,7 +15,9 @@ Geometries (L = 4 levels of an 800 x 1333 frame: 100x167, 50x84, 25x42, 13x21; -
                          map still needs its gradient): no value gradient, the LDS grad_value kernel must not run
 Here the routes are those of grad_value in dfx.ops.msda_fused_backward where the tree has the switch (dfx.ops.USE_LEVEL_BWD):
 "lds" (csrc/msda_level_backward.hip) and "atomics" alternate in one process; a tree without it has "atomics" only.  The
-launches of the LDS kernel in one pass are counted and printed.
+launches of the LDS kernel in one pass are counted and printed.  --deterministic adds the fixed-point twin of each route
+("lds-fixed", "atomics-fixed": dfx.ops.deterministic_mode() forced on, csrc/fixed_sum.h) to the alternation and prints
+fixed / float per route.
 
 Where the module has the MSDA_TRAIN switch (models/ops/modules/ms_deform_attn.py) the two routes - fused forward + fused
 backward, and the operator sequence with MSDeformAttnFunction - alternate in one process, --reps times each; elsewhere
@@ -26,7 +28,7 @@ of forward, backward and total, and torch.cuda.max_memory_allocated of one pass 
 Nothing is asserted.
 
     python tools/bench_msda_train.py [--iters 20] [--warmup 3] [--reps 5] [--frames 4] [--set multi|single] [--only GEOMETRY]
-                                     [--pkg DIR] [--label NAME]
+                                     [--deterministic] [--pkg DIR] [--label NAME]
 """
 import argparse
 import os
@@ -43,7 +45,7 @@ GEOMETRIES = [("encoder", None, 2, True, 1), ("decoder", 300, 2, True, 25), ("de
               ("decoder-box", 300, 4, True, 25)]
 SINGLE_SIZES = [(50, 84)]
 SINGLE_GEOMETRIES = [("encoder-1l", None, 2, True, 10), ("decoder-1l", 300, 2, True, 25), ("encoder-1l-detached", None, 2, False, 10)]
-LEVEL_ENTRY = "dfx_msda_level_grad_value_f32"
+LEVEL_ENTRIES = ("dfx_msda_level_grad_value_f32", "dfx_msda_level_grad_value_fixed_f32")
 
 
 def one_pass(fn, leaves, gout, iters, warmup):
@@ -69,6 +71,7 @@ def main():
     ap.add_argument("--frames", type=int, default=4)
     ap.add_argument("--set", choices=("multi", "single"), default="multi")
     ap.add_argument("--only", default=None, help="time this geometry alone")
+    ap.add_argument("--deterministic", action="store_true", help="--set single: time the fixed-point twins as well")
     ap.add_argument("--pkg", default=os.path.join(ROOT, "depth-fusion-in-transformer-based-video-object-detection_amd"))
     ap.add_argument("--label", default="this tree")
     args = ap.parse_args()
@@ -82,12 +85,17 @@ def main():
     if single:
         switch = hasattr(ops, "USE_LEVEL_BWD")
         routes = [("lds", True), ("atomics", False)] if switch else [("atomics", None)]
+        if args.deterministic:      # (route, LDS switch, deterministic mode)
+            assert switch and hasattr(ops, "deterministic_mode"), "this tree has no deterministic mode"
+            routes = [(r + tail, (on, det)) for r, on in routes for tail, det in (("", "0"), ("-fixed", "1"))]
     else:
         switch = hasattr(mod_file, "MSDA_TRAIN")
         routes = [("fused", True), ("operator", False)] if switch else [("operator", None)]
 
     def take(on):
-        if switch and single:
+        if switch and single and args.deterministic:
+            ops.USE_LEVEL_BWD, ops._DETERMINISTIC_ENV = on
+        elif switch and single:
             ops.USE_LEVEL_BWD = on
         elif switch:
             mod_file.MSDA_TRAIN = on
@@ -150,7 +158,7 @@ def main():
                     torch.cuda.synchronize()
                 finally:
                     ops._call = real_call
-                lds_launches[r] = launches.count(LEVEL_ENTRY)
+                lds_launches[r] = sum(launches.count(e) for e in LEVEL_ENTRIES)
         tag = f"[{args.label}] [{name:16s} Lq {Lq:6d} ref_dim {ref_dim} passes {iters:4d}]"
         med = {}
         for r, _ in routes:
@@ -162,7 +170,10 @@ def main():
                   + (f"  LDS grad_value launches per pass {lds_launches[r]}" if r in lds_launches else ""))
         if switch and single:
             print(f"{tag} atomics / lds {med['atomics'] / med['lds']:5.2f}x")
-            take(True)
+            if args.deterministic:
+                print(f"{tag} fixed / float: lds {med['lds-fixed'] / med['lds']:5.2f}x  atomics {med['atomics-fixed'] / med['atomics']:5.2f}x"
+                      f"   atomics-fixed / lds-fixed {med['atomics-fixed'] / med['lds-fixed']:5.2f}x")
+            take((True, None) if args.deterministic else True)
         elif switch:
             print(f"{tag} operator / fused {med['operator'] / med['fused']:5.2f}x   peak memory {peak['operator'] / 1e6:.1f} -> "
                   f"{peak['fused'] / 1e6:.1f} MB")

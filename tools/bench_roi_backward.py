@@ -5,13 +5,15 @@
 Prints, per box set and per kernel form (merged per-axis taps / plain four adds per sample, DFX_ROI_BWD_PLAIN):
 time per launch from HIP events around --iters launches after --warmup (the entry point's zero fill of grad_input
 included), the atomic bytes added per launch (host-side count of pixel rows x C x 4 bytes), bytes / time, and the
-forward's time on the same inputs.  Nothing is asserted.
+forward's time on the same inputs.  Nothing is asserted.  --deterministic times the fixed-point twin of each form
+(csrc/fixed_sum.h: int64 workspace zero fill, absmax, adds, convert) alternating with the float form, --reps times each,
+and prints medians, every repetition and fixed / float.
 
 Box sets: "image" = boxes of an 800 x 1344 image, which spatial_scale 1/32 puts on the top-left 25 x 42 of the
 stride-16 map (the quirk of the reference that the model keeps); "map" = boxes spread over the whole 50 x 84 map.
 Both: centres uniform over the area widened by 10 % a side, sides 1/16 .. 1/2 of the area's.
 
-    python tools/bench_roi_backward.py [--iters 20] [--warmup 3]
+    python tools/bench_roi_backward.py [--iters 20] [--warmup 3] [--deterministic [--reps 5]]
 """
 import argparse
 import os
@@ -82,7 +84,10 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--deterministic", action="store_true")
+    ap.add_argument("--reps", type=int, default=5)
     args = ap.parse_args()
+    import statistics
     from dfx import ops
     g = torch.Generator().manual_seed(1)
     x = torch.randn(N, H, W, C, generator=g).cuda()
@@ -101,8 +106,15 @@ def main():
             else:
                 os.environ["DFX_ROI_BWD_PLAIN"] = env
             ops.reload_tuning()
-            t = timed(lambda: ops.roi_align_backward(go, r, (N, H, W, C), SIZE, SCALE, SR, True, channels_last=True),
-                      args.iters, args.warmup)
+            run = lambda det=False: timed(lambda: ops.roi_align_backward(go, r, (N, H, W, C), SIZE, SCALE, SR, True,
+                                                                        channels_last=True, **({"deterministic": True} if det else {})),
+                                          args.iters, args.warmup)
+            if args.deterministic:
+                reps = [(run(False), run(True)) for _ in range(args.reps)]
+                flt, fix = statistics.median(a for a, _ in reps), statistics.median(b for _, b in reps)
+                print(f"[{name}] backward {form:6s} float {flt * 1e6:9.1f} us  fixed {fix * 1e6:9.1f} us  fixed / float {fix / flt:5.2f}x  "
+                      f"reps (float, fixed) {' '.join(f'({a * 1e6:.1f}, {b * 1e6:.1f})' for a, b in reps)}")
+            t = run()
             nbytes = rows * C * 4
             print(f"[{name}] backward {form:6s} {t * 1e6:9.1f} us   {rows / bins:5.2f} atomic rows / bin   "
                   f"{nbytes / 1e9:6.3f} GB added   {nbytes / t / 1e12:5.2f} TB/s   "
