@@ -71,6 +71,11 @@ SIGNATURES = {
     "dfx_bias_act_nchw_f32": [_p, _p, _p, _p, _i, _i, _l, _i, _p],
     "dfx_bias_relu_maxpool_f32": [_p, _p, _p, _i, _i, _i, _i, _p],
     "dfx_add_layernorm_f32": [_p, _p, _p, _p, _p, _l, _i, ctypes.c_float, _p],
+    # x, res | NULL, mask | NULL, gamma, beta, out, s, mean, rstd, keep | NULL, rows, C, eps, stream (csrc/layernorm_train.hip)
+    "dfx_add_layernorm_train_f32": [_p] * 10 + [_l, _i, ctypes.c_float, _p],
+    # dy, s, mean, rstd, gamma, keep | NULL, scale, grad_x | NULL, grad_res | NULL, grad_gamma | NULL, grad_beta | NULL,
+    # workspace | NULL, rows, C, stream
+    "dfx_add_layernorm_backward_f32": [_p] * 6 + [ctypes.c_float] + [_p] * 5 + [_l, _i, _p],
     "dfx_box_refine_f32": [_p, _p, _i, _p, _l, ctypes.c_float, _p],
     "dfx_group_norm_f32": [_p, _p, _p, _p, _p, _i, _i, _l, _i, ctypes.c_float, _i, _p],
     # dy, x, stats, gamma, dx | NULL, dgamma | NULL, dbeta | NULL, workspace, N, C, HW, groups, dy_tokens, stream

@@ -1242,6 +1242,125 @@ def add_layernorm(x, residual, norm):
     return out
 
 
+ADDLN_BWD_ROWS_PER_BLOCK, ADDLN_BWD_MAX_GRID = 16, 1024      # DFX_ADDLN_BWD_* of include/dfx_fused.h
+
+
+def add_layernorm_backward_grid(rows):
+    """Workgroups of the backward launch = rows of its workspace (DFX_ADDLN_BWD_GRID): a function of ``rows`` alone."""
+    return min((rows + ADDLN_BWD_ROWS_PER_BLOCK - 1) // ADDLN_BWD_ROWS_PER_BLOCK, ADDLN_BWD_MAX_GRID)
+
+
+def _addln_rows(what, x, C):
+    _require(x.dim() >= 1 and x.dtype == torch.float32 and x.shape[-1] == C and C % 4 == 0 and 0 < C <= 1024,
+             f"{what}: fp32 rows of C columns, C a multiple of 4 and <= 1024")
+    return x.numel() // C
+
+
+def add_layernorm_train_forward(x, residual, weight, bias, eps, mask=None):
+    """``LayerNorm(residual + x * mask)`` with what its backward reads (include/dfx_fused.h, dfx_add_layernorm_train_f32):
+    -> (out, s, mean, rstd, keep).  s = residual + x * mask, fp32 like x; mean, rstd [rows]; keep uint8 like x, 1 where
+    mask != 0, None without a mask.  residual and mask (fp32, x's shape, 0 or 1/(1-p)) may be None.  No autograd node.
+    Without a mask ``out`` has the bits of ``add_layernorm``, with one those of ``add_layernorm(x * mask, residual)``."""
+    C = weight.numel()
+    x2 = x.contiguous()
+    named = [("x", x2), ("weight", weight), ("bias", bias)]
+    for nm, t in (("residual", residual), ("mask", mask)):
+        if t is not None:
+            _require(t.shape == x.shape and t.dtype == torch.float32, f"add_layernorm_train: {nm} must match x")
+            named.append((nm, t.contiguous()))
+    _check_inputs(named)
+    rows = _addln_rows("add_layernorm_train", x2, C)
+    _require(weight.dtype == torch.float32 and bias.dtype == torch.float32 and bias.numel() == C,
+             "add_layernorm_train: fp32 weight and bias of C elements")
+    residual, mask = (dict(named).get(nm) for nm in ("residual", "mask"))
+    out, s = torch.empty_like(x2), torch.empty_like(x2)
+    mean = torch.empty((rows,), dtype=torch.float32, device=x2.device)
+    rstd = torch.empty((rows,), dtype=torch.float32, device=x2.device)
+    keep = None if mask is None else torch.empty(x2.shape, dtype=torch.uint8, device=x2.device)
+    _call("add_layernorm_train", "dfx_add_layernorm_train_f32", x2.device, x2.data_ptr(), _ptr(residual), _ptr(mask),
+          weight.data_ptr(), bias.data_ptr(), out.data_ptr(), s.data_ptr(), mean.data_ptr(), rstd.data_ptr(), _ptr(keep),
+          rows, C, float(eps))
+    return out, s, mean, rstd, keep
+
+
+def add_layernorm_backward(grad_out, s, mean, rstd, weight, keep=None, scale=1.0, need_x=True, need_residual=True,
+                           need_gamma=True, need_beta=True):
+    """Gradients of ``add_layernorm_train_forward`` (include/dfx_fused.h, dfx_add_layernorm_backward_f32) ->
+    (grad_x | None, grad_residual | None, grad_gamma | None, grad_beta | None), fresh fp32 tensors; only what is asked
+    for is computed.  Without ``keep`` grad_x and grad_residual are the same values and come back as ONE tensor.
+    Two launches without atomics, sums in a fixed order: two calls give the same bits."""
+    C = weight.numel()
+    grad_out = grad_out.contiguous()
+    named = [("grad_out", grad_out), ("s", s), ("mean", mean), ("rstd", rstd), ("weight", weight)]
+    if keep is not None:
+        named.append(("keep", keep))
+        _require(keep.dtype == torch.uint8 and keep.shape == s.shape, "add_layernorm_backward: keep must be uint8 of s's shape")
+    _check_inputs(named)
+    rows = _addln_rows("add_layernorm_backward", s, C)
+    _require(grad_out.dtype == torch.float32 and grad_out.shape == s.shape and weight.dtype == torch.float32
+             and mean.dtype == torch.float32 and rstd.dtype == torch.float32 and mean.numel() == rows and rstd.numel() == rows,
+             "add_layernorm_backward: fp32 grad_out of s's shape, mean and rstd of one element per row")
+    dev = s.device
+    shared = keep is None and need_x and need_residual
+    grad_x = torch.empty_like(s) if need_x else None
+    grad_res = grad_x if shared else torch.empty_like(s) if need_residual else None
+    new = torch.zeros if rows == 0 else torch.empty
+    grad_gamma = new((C,), dtype=torch.float32, device=dev) if need_gamma else None
+    grad_beta = new((C,), dtype=torch.float32, device=dev) if need_beta else None
+    if rows > 0 and (need_x or need_residual or need_gamma or need_beta):
+        ws = (torch.empty((add_layernorm_backward_grid(rows), 2 * C), dtype=torch.float32, device=dev)
+              if need_gamma or need_beta else None)
+        _call("add_layernorm_backward", "dfx_add_layernorm_backward_f32", dev, grad_out.data_ptr(), s.data_ptr(), mean.data_ptr(),
+              rstd.data_ptr(), weight.data_ptr(), _ptr(keep), float(scale), _ptr(grad_x), None if shared else _ptr(grad_res),
+              _ptr(grad_gamma), _ptr(grad_beta), _ptr(ws), rows, C)
+    return grad_x, grad_res, grad_gamma, grad_beta
+
+
+class _AddLayerNormFunction(torch.autograd.Function):
+    """apply(x, residual | None, weight, bias, mask | None, eps, scale): saves s, mean, rstd, the 1-byte keep mask and the
+    weight - what the library's add + LayerNorm + dropout nodes save, and not the float mask."""
+
+    @staticmethod
+    def forward(ctx, x, residual, weight, bias, mask, eps, scale):
+        out, s, mean, rstd, keep = add_layernorm_train_forward(x, residual, weight, bias, eps, mask)
+        ctx.save_for_backward(s, mean, rstd, keep, weight)
+        ctx.scale = scale
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        s, mean, rstd, keep, weight = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        # (looked up at call time: tests wrap it)
+        gx, gr, gg, gb = add_layernorm_backward(grad_output, s, mean, rstd, weight, keep, ctx.scale, need_x=need[0],
+                                                need_residual=need[1], need_gamma=need[2], need_beta=need[3])
+        return gx, gr, gg, gb, None, None, None
+
+
+def add_layernorm_train(x, residual, norm, dropout=None):
+    """``norm(residual + dropout(x))`` for an nn.LayerNorm over the last dimension - the tail of a transformer sub-layer -
+    in one launch, with an autograd node whose backward is two (``add_layernorm_backward``); residual may be None.
+    dropout: the sub-layer's nn.Dropout.  When it is live (training, p > 0) the mask is drawn as
+    ``F.dropout(ones_like(x), p, True)`` right here, where the module would call ``F.dropout(x, p, True)``: the same shape
+    from the same generator gives the same numbers (the rule of models.fused_mha.attention_dropout_mask), so under a fixed
+    seed both routes drop the same elements and x * mask has the bits of the module's output.
+    Without grad mode, or when neither x, residual nor the norm's parameters require a gradient, no node is made."""
+    import torch.nn.functional as F
+    _require(isinstance(norm, torch.nn.LayerNorm) and len(norm.normalized_shape) == 1 and norm.weight is not None
+             and norm.bias is not None, "add_layernorm_train: an affine nn.LayerNorm over the last dimension")
+    _require(residual is None or residual.shape == x.shape, "add_layernorm_train: residual must match x")
+    _addln_rows("add_layernorm_train", x, norm.weight.numel())
+    mask, scale = None, 1.0
+    if dropout is not None and dropout.training and dropout.p > 0:
+        mask = F.dropout(torch.ones_like(x), dropout.p, True)
+        scale = 1.0 / (1.0 - dropout.p) if dropout.p < 1 else 0.0
+    if torch.is_grad_enabled() and (x.requires_grad or (residual is not None and residual.requires_grad)
+                                    or norm.weight.requires_grad or norm.bias.requires_grad):
+        return _AddLayerNormFunction.apply(x, residual, norm.weight, norm.bias, mask, float(norm.eps), scale)
+    return add_layernorm_train_forward(x, residual, norm.weight, norm.bias, norm.eps, mask)[0]
+
+
 def bias_relu_maxpool(x, bias):
     """maxpool3x3/s2/p1(relu(x + bias[c])) on NCHW in one pass: the ResNet stem's epilogue
     (include/dfx_fused.h)."""

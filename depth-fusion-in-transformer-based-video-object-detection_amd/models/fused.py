@@ -38,6 +38,18 @@ CONVGN_TRAIN = os.environ.get("DFX_CONVGN_TRAIN", "1") != "0"
 # 8-15 % slower - a handful of short launches issued from Python against the library's C++ nodes - so smaller maps keep
 # nn.Sequential (tools/bench_convgn_train.py, profiles/r15_convgn_train.txt).
 CONVGN_TRAIN_MIN_PIXELS = 12 * 50 * 84
+# The tail of every sub-layer, norm(residual + dropout(y)), in grad mode on dfx.ops.add_layernorm_train (csrc/layernorm_train.hip: one
+# forward launch, two backward launches, the module's own dropout draw) instead of nn.Dropout + add + nn.LayerNorm under autograd;
+# DFX_ADDLN_TRAIN=0 keeps the modules (A/B measurements).  Read once at import.  Taken by apply_post, transformer_layers._norm_add and
+# the norm(residual + dropout(.)) form of transformer_layers._linear_norm_add for fp32 GPU tensors outside autocast with C % 4 == 0,
+# C <= 1024, something to differentiate (needs_grad) and no hooks on the norm or the dropout.
+ADDLN_TRAIN = os.environ.get("DFX_ADDLN_TRAIN", "1") != "0"
+# The smallest row count at which one tail MEASURED faster than the parent commit's modules beyond the repetition spread: 32 frames of
+# 4200 tokens (1.84x with a live dropout, 2.60x without).  12 x 4200 rows tie (1.02x, and 1.26x inside a spread that reaches the parent's
+# figure); 4 x 4200 rows and fewer are 20-23 % slower - one tail there is host time, ~0.2 ms whatever the row count, and this route's
+# Python node costs more of it than the library's C++ nodes - so fewer rows keep the modules (tools/bench_addln_train.py,
+# profiles/r17_addln_train.txt).
+ADDLN_TRAIN_MIN_ROWS = 32 * 4200
 
 
 def needs_grad(part, *tensors):
@@ -85,11 +97,31 @@ def post_is_fusable(post):
     return drop is None or not drop.training or drop.p == 0
 
 
+def addln_train_usable(norm, dropout, x, residual):
+    """May ``norm(residual + dropout(x))`` run on dfx.ops.add_layernorm_train?  Only as the ADDLN_TRAIN comment says; anything
+    else keeps the modules.  (The switch and the size rule are read here, at call time, from this module's globals.)"""
+    if not (ADDLN_TRAIN and torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.float32 and not torch.is_autocast_enabled()):
+        return False
+    C = x.shape[-1] if x.dim() else 0
+    if not (type(norm) is nn.LayerNorm and tuple(norm.normalized_shape) == (C,) and norm.elementwise_affine and norm.bias is not None
+            and C % 4 == 0 and 0 < C <= 1024 and x.numel() > 0 and x.numel() // C >= ADDLN_TRAIN_MIN_ROWS
+            and norm.weight.dtype == torch.float32 and norm.weight.device == x.device):
+        return False
+    if residual is not None and not (residual.shape == x.shape and residual.dtype == torch.float32 and residual.device == x.device):
+        return False
+    if dropout is not None and (type(dropout) is not nn.Dropout or dropout.inplace or has_hooks(dropout)):
+        return False
+    return not has_hooks(norm) and needs_grad(norm, x, residual)
+
+
 def apply_post(post, out):
     """norm(residual + dropout(out)) for post = (residual, norm[, dropout]); ``out`` itself when post is None."""
     if post is None:
         return out
     drop = post[2] if len(post) > 2 else None
+    if addln_train_usable(post[1], drop, out, post[0]):
+        from dfx import ops
+        return ops.add_layernorm_train(out, post[0], post[1], drop)
     if drop is not None:
         out = drop(out)
     return post[1](post[0] + out)

@@ -116,7 +116,7 @@ class RCNNHead(nn.Module):
             q = fused_mha.forward(self.self_attn, pf, pf, pf, post=(pf, self.norm1, self.dropout1)).reshape(1, N * nr_boxes, self.d_model)
         else:
             attn = self.self_attn(q, q, value=q)[0]
-            q = _norm_add(self.norm1, q, self.dropout1(attn))
+            q = _norm_add(self.norm1, q, attn, dropout=self.dropout1)
             q = q.view(nr_boxes, N, self.d_model).permute(1, 0, 2).reshape(1, N * nr_boxes, self.d_model)
         return q
 

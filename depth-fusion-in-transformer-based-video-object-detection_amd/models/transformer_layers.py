@@ -17,7 +17,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from models.fused import Linear, apply_post
+from models.fused import Linear, addln_train_usable, apply_post
 
 from models.ops.modules import MSDeformAttn
 from models.ops.modules.ms_deform_attn import project_values
@@ -84,6 +84,9 @@ def _linear_norm_add(linear, x, norm, residual=None, act=None, act_first=False, 
     fn = {None: None, "relu": F.relu, "gelu": F.gelu}[act]
     if fn is not None and act_first:
         y = fn(y)
+    if residual is not None and (fn is None or act_first) and addln_train_usable(norm, dropout, y, residual):
+        from dfx import ops as _ops          # grad mode: the tail on its fused kernel pair (models.fused.ADDLN_TRAIN)
+        return _ops.add_layernorm_train(y, residual, norm, dropout)
     if dropout is not None:
         y = dropout(y)
     if residual is not None:
@@ -93,9 +96,16 @@ def _linear_norm_add(linear, x, norm, residual=None, act=None, act_first=False, 
     return norm(y)
 
 
-def _norm_add(norm, x, y=None):
-    """norm(x + y).  Inference on the GPU: one fused pass (dfx.ops.add_layernorm); otherwise the
-    reference's two ops."""
+def _norm_add(norm, x, y=None, dropout=None):
+    """norm(x + dropout(y)).  Inference on the GPU: one fused pass (dfx.ops.add_layernorm); in grad mode with something to
+    differentiate the fused forward / backward pair (dfx.ops.add_layernorm_train, models.fused.ADDLN_TRAIN); otherwise the
+    reference's ops."""
+    if y is not None:
+        if addln_train_usable(norm, dropout, y, x):
+            from dfx import ops as _ops
+            return _ops.add_layernorm_train(y, x, norm, dropout)
+        if dropout is not None:
+            y = dropout(y)
     if x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled() and x.shape[-1] % 4 == 0 \
             and x.shape[-1] <= 1024:
         from dfx import ops as _ops
@@ -181,7 +191,7 @@ class DeformableTransformerEncoderLayer(nn.Module):
 
     def forward_ffn(self, src):
         y = self.linear2(self.dropout2(self.activation(self.linear1(src))))
-        return _norm_add(self.norm2, src, self.dropout3(y))
+        return _norm_add(self.norm2, src, y, dropout=self.dropout3)
 
     def forward(self, src, pos, reference_points, spatial_shapes, level_start_index, padding_mask=None,
                 rgbd_src=None):
@@ -197,7 +207,7 @@ class DeformableTransformerEncoderLayer(nn.Module):
                                  post=(src, self.norm1, self.dropout1))
         else:
             y = self.self_attn(query, reference_points, src, spatial_shapes, level_start_index, padding_mask)
-            src = _norm_add(self.norm1, src, self.dropout1(y))
+            src = _norm_add(self.norm1, src, y, dropout=self.dropout1)
         if fused and self.activation is F.relu:
             from dfx import ops as _ops            # linear1 + bias + ReLU in one MFMA GEMM, linear2 + residual + LayerNorm in another
             h = _ops.linear(src.contiguous(), self.linear1.weight, self.linear1.bias, relu=True)
@@ -255,7 +265,7 @@ class _CrossFusionBlock(nn.Module):
             return _linear_norm_add(self.linear1, tgt, getattr(self, self._ffn_norm), tgt, act="gelu", act_first=True,
                                     dropout=getattr(self, self._ffn_drop))
         y = self.activation(self.linear1(tgt))
-        return _norm_add(getattr(self, self._ffn_norm), tgt, getattr(self, self._ffn_drop)(y))
+        return _norm_add(getattr(self, self._ffn_norm), tgt, y, dropout=getattr(self, self._ffn_drop))
 
     def _fuse(self, tgt, query_pos, reference_points, src, src_spatial_shapes, src_start_index, src_padding_mask):
         src = _linear_norm_add(self.depth_scale_adapt, src, self.norm_depth_scale)

@@ -35,6 +35,43 @@ int dfx_bias_relu_maxpool_f32(const float *x, const float *bias, float *out, int
 int dfx_add_layernorm_f32(const float *x, const float *res, const float *gamma, const float *beta, float *out,
                           long rows, int C, float eps, void *stream);
 
+/* The same tail under a training step, with the sub-layer's dropout (csrc/layernorm_train.hip):
+ *   s[r,:] = res[r,:] + x[r,:] * mask[r,:],   out[r,:] = LayerNorm(s[r,:]) * gamma + beta
+ * in dfx_add_layernorm_f32's arithmetic and order: without a mask ``out`` has that entry's bits, with one the bits of that
+ * entry run on x * mask (the product is rounded before the add).  Also written, for the backward: s [rows,C], mean and
+ * rstd [rows] each (rstd the correctly rounded 1 / sqrt(var + eps), where ``out`` uses that entry's approximate reciprocal
+ * square root), and - with a mask - keep [rows,C], one byte per element, 1 where mask != 0.
+ *   res, mask (fp32 [rows,C], 0 or 1/(1-p)) may be NULL; keep may be NULL without a mask.
+ * Same limits as dfx_add_layernorm_f32 (C % 4 == 0, C <= 1024, 16-byte aligned float buffers; keep 4-byte aligned);
+ * every check runs before the launch; rows == 0 returns DFX_OK without one. */
+int dfx_add_layernorm_train_f32(const float *x, const float *res, const float *mask, const float *gamma,
+                                const float *beta, float *out, float *s, float *mean, float *rstd, unsigned char *keep,
+                                long rows, int C, float eps, void *stream);
+
+/* Backward of dfx_add_layernorm_train_f32 from what it left.  With xh = (s - mean) * rstd and g = dy * gamma:
+ *   ds[r,:]        = rstd * (g - mean_c(g) - xh * mean_c(g * xh))
+ *   grad_res       = ds                                                   [rows,C]
+ *   grad_x         = ds without ``keep``; with it ds * scale where keep != 0 and 0 elsewhere (scale = 1/(1-p))
+ *   grad_gamma[c]  = sum_r dy * xh,   grad_beta[c] = sum_r dy             [C]
+ * Each of the four outputs may be NULL and its work is then skipped; the others are overwritten, never accumulated into
+ * (plain stores: the buffers need no zero fill).  Without ``keep`` grad_x and grad_res are the same values: ask for one.
+ * No atomics.  The launch has DFX_ADDLN_BWD_GRID(rows) workgroups of four waves - a function of rows alone, no device
+ * query; wave w of 4 * grid walks rows w, w + 4 * grid, ... in ascending order with its columns' sums in registers (the
+ * terms dy * xh of grad_gamma formed and added in fp64, rounded to fp32 once per wave), the
+ * four waves are added in wave order, every workgroup writes row b of ``workspace`` [grid, 2C] (caller-owned, needed for
+ * grad_gamma / grad_beta only), and a second launch adds the rows: 16 contiguous slices, each in ascending order, then
+ * the slices in ascending order.  Two calls give the same bits, on any device.
+ * Checks as the forward, before any launch; rows == 0 launches nothing and zero-fills grad_gamma / grad_beta. */
+#define DFX_ADDLN_BWD_ROWS_PER_BLOCK 16
+#define DFX_ADDLN_BWD_MAX_GRID 1024
+#define DFX_ADDLN_BWD_GRID(rows) \
+    (((rows) + DFX_ADDLN_BWD_ROWS_PER_BLOCK - 1) / DFX_ADDLN_BWD_ROWS_PER_BLOCK < DFX_ADDLN_BWD_MAX_GRID \
+         ? ((rows) + DFX_ADDLN_BWD_ROWS_PER_BLOCK - 1) / DFX_ADDLN_BWD_ROWS_PER_BLOCK : DFX_ADDLN_BWD_MAX_GRID)
+int dfx_add_layernorm_backward_f32(const float *dy, const float *s, const float *mean, const float *rstd,
+                                   const float *gamma, const unsigned char *keep, float scale, float *grad_x,
+                                   float *grad_res, float *grad_gamma, float *grad_beta, float *workspace,
+                                   long rows, int C, void *stream);
+
 /* Box refinement of the iterative decoders and detection heads in one pass:
  *   out[r,c] = sigmoid(delta[r,c] + inverse_sigmoid(ref[r,c]))  for c < ref_dim,  sigmoid(delta[r,c]) otherwise,
  * inverse_sigmoid(x) = log(max(clamp(x,0,1), eps) / max(1 - clamp(x,0,1), eps))
