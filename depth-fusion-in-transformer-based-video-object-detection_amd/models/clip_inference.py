@@ -31,7 +31,7 @@ import torch.distributed as dist
 from util.misc import NestedTensor
 
 from .detector_common import apply_box_head
-from .fused import enable_fused_inference
+from .fused import derived_key, enable_fused_inference
 
 
 class ClipRunner:
@@ -57,7 +57,9 @@ class ClipRunner:
         kernels from Python: the same kernels and bit-equal outputs, the host side of a 4-frame step drops from ~9 ms to
         well under 1 ms (8 ranks share one host).  A lane is then ONE stream with one clip in flight; use 3 lanes, or 4 with
         GPU_MAX_HW_QUEUES=8 (the HIP runtime maps a process's streams onto 4 hardware queues by default: INTEGRATION.md).  Masked
-        (padded) clips take the eager route."""
+        (padded) clips take the eager route.  A captured step launches with the tensors the routes had derived from the
+        weights at capture time; every submit compares ``weights_key()`` with the one the slot was captured under and captures
+        again after a weight update (``refresh()`` for the edits no key can see: models.fused.derived_key)."""
         self.model = model
         self.gather_on_one_rank = gather_on_one_rank
         self.lanes = max(1, int(lanes))
@@ -79,6 +81,35 @@ class ClipRunner:
         if key not in self._const:
             self._const[key] = build()
         return self._const[key]
+
+    # ---- weight updates under captured graphs ------------------------------------------------------------------------------
+    def weights_key(self):
+        """models.fused.derived_key of every parameter and buffer of the model, each once (tied tensors, shared heads).  The
+        walk over the modules is done once per runner; what is kept is (the module's own table, name), not the tensor, so a
+        rebinding (``p.data = t`` keeps the object, ``load_state_dict(assign=True)`` and ``setattr`` of a buffer do not) is
+        seen as the new tensor it is."""
+        src = self.__dict__.get("_key_sources")
+        if src is None:
+            seen, src = set(), []
+            for mod in self.model.modules():
+                for table in (mod._parameters, mod._buffers):
+                    for name, t in table.items():
+                        if t is None or id(t) not in seen:
+                            src.append((table, name))
+                            seen.add(id(t))
+            self._key_sources = src
+        return derived_key(*[table[name] for table, name in src])
+
+    def refresh(self):
+        """Drop every captured graph: the next ``submit`` of a shape captures again, with whatever the fused routes derive from
+        the weights then.  ``submit`` does this by itself when ``weights_key()`` has moved; call it (and
+        models.fused.drop_derived on the model) after an edit the key cannot see.  Waits for the device first: a replay in
+        flight reads the graph's memory pool and the derived tensors of its capture.  -> the number of slots dropped."""
+        n = len(self._graph_slots)
+        if n:
+            torch.cuda.synchronize()
+            self._graph_slots.clear()
+        return n
 
     # ---- steps 1+2 for a block of frames -------------------------------------------------------
     # the two halves of steps 1+2 for ALL frames of the block in one pass (what ``submit`` pipelines)
@@ -322,12 +353,18 @@ class ClipRunner:
             self._streams[skey] = torch.cuda.Stream(dev)
         stream = self._streams[skey]
         key = (skey, tuple(frames.shape), frames.dtype, clips, sharded)
+        weights = self.weights_key()
         slot = self._graph_slots.get(key)
+        if slot and slot["weights"] != weights:                           # a weight update since the capture: all slots are stale
+            self.refresh()
+            slot = None
         cur = torch.cuda.current_stream(dev)
         saved_overlap, self.overlap = self.overlap, False
         try:
             if slot is None:
                 slot = self._capture_slot(frames, clips, first, sharded, stream, cur, skey in self._lane_carried_collectives)
+                if slot:
+                    slot["weights"] = weights
                 self._graph_slots[key] = slot
             if slot is False:                                             # capture failed once (reported then): eager route
                 self.overlap = saved_overlap

@@ -11,7 +11,7 @@ from torch import nn
 
 from util.memo import memo_on
 
-from models.fused import Linear
+from models.fused import Linear, derived_key
 from torch.nn.init import constant_, normal_, xavier_uniform_
 
 from models.ops.modules import MSDeformAttn
@@ -132,7 +132,7 @@ class SpatialTransformerBase(nn.Module):
             else:
                 # positional embedding + level embedding: derived from the (memoised) positional tensor and the
                 # parameter's version, so inference builds it once per mask (util/memo.py)
-                pos.append(memo_on(p, ("lvl_pos", lvl, level_embed.data_ptr(), level_embed._version),
+                pos.append(memo_on(p, ("lvl_pos", lvl) + derived_key(level_embed),
                                    lambda p=p, lvl=lvl: p.flatten(2).transpose(1, 2) + level_embed[lvl].view(1, 1, -1)))
         one = len(tok) == 1                     # a single level: nothing to concatenate (torch.cat would copy)
         return (tok[0] if one else torch.cat(tok, 1), msk[0] if one else torch.cat(msk, 1),

@@ -69,8 +69,8 @@ class _ConvGN(nn.Sequential):
         if conv.kernel_size == (1, 1) and conv.stride == (1, 1) and hw % 4 == 0 and x.shape[1] % 4 == 0:
             y = _ops.conv1x1(x, conv.weight, conv.bias)
         else:
-            key = (conv.weight.data_ptr(), conv.weight._version, None if conv.bias is None else conv.bias._version)
-            if getattr(self, "_plan", (None,))[0] != key:
+            key = _fused.derived_key(conv.weight, conv.bias)
+            if self.__dict__.get("_plan", (None,))[0] != key:
                 self._plan = (key, _ops.ConvPlan(conv.weight, conv.bias, conv.stride, conv.padding, conv.dilation,
                                                  groups=conv.groups, padding_mode=conv.padding_mode))
             y = self._plan[1](x)

@@ -16,7 +16,7 @@ from dfx import ops as _ops
 from util.memo import memo_on
 from util.misc import NestedTensor
 
-from .fused import needs_grad
+from .fused import derived_key, needs_grad
 from .position_encoding import build_position_encoding
 
 
@@ -100,9 +100,8 @@ class DFormerBackbone(nn.Module):
         previous stage's last operation directly (only the last stage's output is returned here), and the zero
         padding of the next convolution is applied after it in both formulations, so the result is the same
         up to rounding."""
-        key = tuple((t.data_ptr(), t._version) for mod in stages.modules() if isinstance(mod, (nn.Conv2d, nn.BatchNorm2d))
-                    for t in list(mod.parameters(recurse=False)) + list(mod.buffers(recurse=False)))
-        if getattr(self, "_folded", None) is None or self._folded[0] != key:
+        key = derived_key(*(mod for mod in stages.modules() if isinstance(mod, (nn.Conv2d, nn.BatchNorm2d))))
+        if self.__dict__.get("_folded") is None or self._folded[0] != key:
             ops = [mod for stage in stages for mod in stage]       # conv, bn, gelu, conv, bn | bn, conv | bn, conv
             plan = []                                              # (weight, bias, stride, padding, gelu_after)
             i = 0

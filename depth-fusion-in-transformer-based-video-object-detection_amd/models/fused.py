@@ -52,6 +52,48 @@ ADDLN_TRAIN = os.environ.get("DFX_ADDLN_TRAIN", "1") != "0"
 ADDLN_TRAIN_MIN_ROWS = 32 * 4200
 
 
+def derived_key(*sources):
+    """The "have the sources changed" key of every tensor kept by an inference route that was DERIVED from weights (folded BN,
+    transformed / re-ordered filters, stacked projection matrices, captured graphs): a tuple of ``(data_ptr, _version)``, one
+    entry per source tensor.  A module stands for its own parameters and buffers (``recurse=False``), in definition order; a
+    ``None`` (a missing bias) stays ``None``.  The version counter moves under every in-place write that autograd sees
+    (``optimizer.step()``, ``load_state_dict``, ``with no_grad(): p.mul_()``), the pointer under every rebinding
+    (``p.data = new``, ``load_state_dict(assign=True)``, ``setattr`` of a buffer) - which leaves the counter where it was.
+    In-place writes through ``.data`` (``p.data.mul_()``) move neither: ``drop_derived`` is for those."""
+    out = []
+    for s in sources:
+        if s is None:
+            out.append(None)
+        elif isinstance(s, nn.Module):
+            out.extend(None if t is None else (t.data_ptr(), t._version) for t in (*s._parameters.values(), *s._buffers.values()))
+        else:
+            out.append((s.data_ptr(), s._version))
+    return tuple(out)
+
+
+# every attribute a fused inference route keeps derived tensors in, by the module that holds it (INTEGRATION.md, DESIGN.md 4g)
+DERIVED_ATTRIBUTES = ("_folded", "_plans1x1", "_chain_carry", "_stem_folded",                   # models/resnet.py, models/dformer_backbone.py
+                      "_plan",                                                                   # models/detector_common.py
+                      "_qproj_cache", "_qproj_head", "_qproj_head_key", "_value_stack",          # models/ops/modules/ms_deform_attn.py
+                      "_kv_stack")                                                               # models/fused_mha.py
+
+
+def drop_derived(model):
+    """Forget every tensor the fused inference routes of ``model`` derived from its weights: the DERIVED_ATTRIBUTES of every
+    submodule and the whole of ``util.memo``.  The next call rebuilds them, exactly as a module that has never run would.
+    For edits no key can see (``derived_key``), and for whoever wants the memory back.  -> the number of entries dropped.
+    (A ``ClipRunner(graph=True)`` keeps captured launches of its own: ``ClipRunner.refresh()``.)"""
+    from util import memo
+    n = 0
+    for mod in model.modules():
+        for name in DERIVED_ATTRIBUTES:
+            if mod.__dict__.pop(name, None) is not None:
+                n += 1
+    n += len(memo._MEMO)
+    memo.clear()
+    return n
+
+
 def needs_grad(part, *tensors):
     """Does running ``part`` (a module, or an iterable of parameters) on ``tensors`` have anything to differentiate?  True only
     when grad mode is on and one of the tensors or one of the part's parameters requires a gradient.  The front of the detector

@@ -19,7 +19,7 @@ import torch.nn.functional as F
 
 from dfx import ops as _ops
 
-from .fused import apply_post, has_hooks, post_is_fusable
+from .fused import apply_post, derived_key, has_hooks, post_is_fusable
 
 # grad mode on the fused attention forward + backward; DFX_MHA_TRAIN=0 keeps nn.MultiheadAttention itself (A/B runs).
 # Read once at import.
@@ -61,8 +61,8 @@ def project_kv_stack(mhas, pool):
     contiguous [rows, 2E] tensor: dfx.ops.linear(col_block=2E)) - the three temporal query encoders of TransVOD++ pick from one
     pool of reference queries.  -> list of [rows, 2E]"""
     E = mhas[0].embed_dim
-    key = tuple((m.in_proj_weight.data_ptr(), m.in_proj_weight._version, m.in_proj_bias._version) for m in mhas)
-    cache = getattr(mhas[0], "_kv_stack", None)
+    key = derived_key(*(t for m in mhas for t in (m.in_proj_weight, m.in_proj_bias)))
+    cache = mhas[0].__dict__.get("_kv_stack")
     if cache is None or cache[0] != key:
         cache = (key, torch.cat([m.in_proj_weight[E:] for m in mhas], 0).contiguous(),
                  torch.cat([m.in_proj_bias[E:] for m in mhas], 0).contiguous())

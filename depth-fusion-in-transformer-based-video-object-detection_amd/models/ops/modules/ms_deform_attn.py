@@ -28,7 +28,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from models.fused import Linear, apply_post, post_is_fusable
+from models.fused import Linear, apply_post, derived_key, post_is_fusable
 
 from dfx import ops as _ops
 from ..functions import ms_deform_attn_func as _func
@@ -60,7 +60,6 @@ class MSDeformAttn(nn.Module):
         self.attention_weights = Linear(d_model, mlp)
         self.value_proj = Linear(d_model, d_model)
         self.output_proj = Linear(d_model, d_model)
-        self._qproj_cache = None
         self._reset_parameters()
 
     def _reset_parameters(self):
@@ -84,9 +83,9 @@ class MSDeformAttn(nn.Module):
     # -- one GEMM for both query projections (weights concatenated lazily, refreshed when edited) --
     def _qproj_params(self):
         so, aw = self.sampling_offsets, self.attention_weights
-        key = (so.weight._version, so.bias._version, aw.weight._version, aw.bias._version,
-               so.weight.data_ptr(), aw.weight.data_ptr(), so.weight.device, so.weight.dtype)
-        if self._qproj_cache is None or self._qproj_cache[0] != key:
+        key = derived_key(so.weight, so.bias, aw.weight, aw.bias) + (so.weight.device, so.weight.dtype)
+        cache = self.__dict__.get("_qproj_cache")
+        if cache is None or cache[0] != key:
             w = torch.cat([so.weight.detach(), aw.weight.detach()], 0).contiguous()
             b = torch.cat([so.bias.detach(), aw.bias.detach()], 0).contiguous()
             self._qproj_cache = (key, w, b)
@@ -97,7 +96,7 @@ class MSDeformAttn(nn.Module):
         (n_levels == 1) - so that a col_block=12 GEMM writes what one workgroup of the level-in-LDS kernel
         reads as one contiguous slab."""
         w, b = self._qproj_params()
-        if self._qproj_cache[0] != getattr(self, "_qproj_head_key", None):
+        if self._qproj_cache[0] != self.__dict__.get("_qproj_head_key"):
             M, P = self.n_heads, self.n_points
             so = torch.arange(M * P * 2, device=w.device).view(M, P * 2)
             aw = torch.arange(M * P, device=w.device).view(M, P) + M * P * 2
@@ -237,9 +236,8 @@ def project_values(attns, input_flatten, input_padding_mask=None):
             or C % 128 != 0 or any(a.d_model != C or a.value_proj.weight.dtype != torch.float32 or a.value_proj.bias is None
                                    or a.value_proj.weight.device != input_flatten.device for a in attns)):
         return None
-    key = tuple((a.value_proj.weight.data_ptr(), a.value_proj.weight._version, a.value_proj.bias.data_ptr(), a.value_proj.bias._version)
-                for a in attns)
-    cache = getattr(first, "_value_stack", None)
+    key = derived_key(*(t for a in attns for t in (a.value_proj.weight, a.value_proj.bias)))
+    cache = first.__dict__.get("_value_stack")
     if cache is None or cache[0] != key:
         cache = (key, torch.cat([a.value_proj.weight for a in attns], 0).contiguous(),
                  torch.cat([a.value_proj.bias for a in attns], 0).contiguous())

@@ -15,7 +15,7 @@ import os
 
 from dfx import ops as _ops
 
-from .fused import needs_grad
+from .fused import derived_key, needs_grad
 
 _PAIR_SHORTCUT = os.environ.get("DFX_PAIR_SHORTCUT", "1") == "1"      # A/B switch of the fused conv3 + shortcut product
 _CONV_CHAIN = os.environ.get("DFX_CONV_CHAIN", "1") == "1"            # A/B switch of conv3 + the next block's conv1 in one launch
@@ -28,14 +28,6 @@ def _fold(conv, bn):
     """Conv weight with the frozen-BN scale folded in, and the remaining per-channel shift."""
     scale, shift = bn.scale_shift()
     return (conv.weight.detach() * scale.reshape(-1, 1, 1, 1)).contiguous(), shift.detach().contiguous()
-
-
-def _versions(*mods):
-    out = []
-    for m in mods:
-        for t in list(m.parameters(recurse=False)) + list(m.buffers(recurse=False)):
-            out.append((t.data_ptr(), t._version))
-    return tuple(out)
 
 
 class Bottleneck(nn.Module):
@@ -51,14 +43,13 @@ class Bottleneck(nn.Module):
         self.bn3 = norm_layer(planes * 4)
         self.relu = nn.ReLU(inplace=True)
         self.downsample = downsample
-        self._folded = None
 
     def _folded_params(self):
         mods = [self.conv1, self.bn1, self.conv2, self.bn2, self.conv3, self.bn3]
         if self.downsample is not None:
             mods += [self.downsample[0], self.downsample[1]]
-        key = _versions(*mods)
-        if self._folded is None or self._folded[0] != key:
+        key = derived_key(*mods)
+        if self.__dict__.get("_folded") is None or self._folded[0] != key:
             c2 = self.conv2
             scale2, shift2 = self.bn2.scale_shift()
             # conv2 on the hand-written kernels (Winograd F(2x2,3x3) for stride 1 incl. the dilated stage,
@@ -178,8 +169,8 @@ class ResNet50(nn.Module):
     def stem(self, x, fused=False):
         if not fused:
             return self.maxpool(self.relu(self.bn1(self.conv1(x))))
-        key = _versions(self.conv1, self.bn1)
-        if getattr(self, "_stem_folded", None) is None or self._stem_folded[0] != key:
+        key = derived_key(self.conv1, self.bn1)
+        if self.__dict__.get("_stem_folded") is None or self._stem_folded[0] != key:
             scale, shift = self.bn1.scale_shift()
             self._stem_folded = (key, (_ops.ConvPlan(self.conv1.weight, None, 2, 3, 1, None, scale=scale.detach()),
                                        shift.detach().contiguous()))
