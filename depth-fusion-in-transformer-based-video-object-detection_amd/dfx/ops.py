@@ -1372,6 +1372,20 @@ def bias_relu_maxpool(x, bias):
     return out
 
 
+def _conv_batch_ranges(algo, N, per_image, image_stride, limit):
+    """The image ranges [(n0, n1), ...] of ConvPlan's launches for a batch of N images of ``per_image`` elements each
+    (``image_stride`` apart when the input is a channel slice read in place, else 0).  Winograd: one launch while the batch
+    stays below ``limit`` elements, else as many whole images as fit below it; the tile kernel: as many images as span at most
+    ``limit`` elements; the implicit GEMM: one launch.  Always at least one image per launch; an empty batch launches nothing."""
+    step = N
+    if algo == "wino" and N * per_image >= limit:
+        step = (limit - 1) // per_image
+    if algo == "tile":
+        step = min(N, limit // max(image_stride, per_image))
+    step = max(1, step)
+    return [(n0, min(N, n0 + step)) for n0 in range(0, N, step)]
+
+
 class ConvPlan:
     """One convolution prepared for the hand-written kernels (include/dfx_conv.h): 3x3 / stride 1 / "same"
     convolutions with Ci % 8 == 0 and Co % 64 == 0 run as fused Winograd F(2x2, 3x3) (weights pre-transformed
@@ -1383,6 +1397,7 @@ class ConvPlan:
     ``weight`` is [Co, Ci, kh, kw] of an ungrouped convolution with zero padding: callers hand over ``conv.groups`` /
     ``conv.padding_mode`` (or check them) - anything else raises."""
     WINO_MAX_ELEMENTS = 1 << 30      # input elements per Winograd launch (32-bit offsets in the kernel); more go in image ranges
+    TILE_MAX_ELEMENTS = (1 << 30) - 4  # ... per tile-kernel launch, image strides included (32-bit byte offsets: below 4 GiB)
 
     def __init__(self, weight, bias=None, stride=1, padding=0, dilation=1, act=None, scale=None, algo=None, groups=1,
                  padding_mode="zeros"):
@@ -1445,14 +1460,9 @@ class ConvPlan:
             x = x.contiguous()
         Ho, Wo = self.out_size(H, W)
         y = torch.empty((N, self.Co, Ho, Wo), dtype=torch.float32, device=x.device)
-        step = N
-        if self.algo == "wino" and N * self.Ci * H * W >= self.WINO_MAX_ELEMENTS:
-            step = max(1, (self.WINO_MAX_ELEMENTS - 1) // (self.Ci * H * W))
-        if self.algo == "tile":           # 32-bit byte offsets over the images of a launch: below 4 GiB per launch
-            step = max(1, min(N, ((1 << 30) - 4) // max(image_stride, self.Ci * H * W)))
+        limit = {"wino": self.WINO_MAX_ELEMENTS, "tile": self.TILE_MAX_ELEMENTS}.get(self.algo)
         with _on(x.device):
-            for n0 in range(0, N, step):
-                n1 = min(N, n0 + step)
+            for n0, n1 in _conv_batch_ranges(self.algo, N, self.Ci * H * W, image_stride, limit):
                 xs, ys = x[n0:n1], y[n0:n1]
                 if self.algo == "wino":
                     _call("conv wino", "dfx_conv3x3_wino_f32", x.device, xs.data_ptr(), self.u.data_ptr(), _ptr(self.bias),
