@@ -81,6 +81,11 @@ SIGNATURES = {
     # dy, x, stats, gamma, dx | NULL, dgamma | NULL, dbeta | NULL, workspace, N, C, HW, groups, dy_tokens, stream
     # (csrc/groupnorm_backward.hip)
     "dfx_group_norm_backward_f32": [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _l, _i, _i, _p],
+    # x, gamma, beta, running_mean | NULL, running_var | NULL, y | NULL, stats, workspace, N, C, HW, eps, momentum, act, stream
+    # (csrc/batchnorm_train.hip)
+    "dfx_batch_norm_train_f32": [_p] * 8 + [_i, _i, _l, ctypes.c_double, ctypes.c_double, _i, _p],
+    # dy, x, stats, gamma, beta, dx | NULL, dgamma | NULL, dbeta | NULL, workspace, N, C, HW, eps, act, stream
+    "dfx_batch_norm_backward_f32": [_p] * 9 + [_i, _i, _l, ctypes.c_double, _i, _p],
     # include/dfx_conv.h
     "dfx_conv2d_igemm_f32": [_p, _p, _p, _p, _p] + [_i] * 14 + [_l, _p],
     "dfx_conv2d_tile_fits": [_i] * 6,

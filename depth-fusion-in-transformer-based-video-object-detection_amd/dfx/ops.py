@@ -1558,3 +1558,112 @@ def group_norm(x, norm, tokens_out=False):
     else:
         y = _group_norm_forward(x, norm.weight, norm.bias, norm.num_groups, norm.eps, tokens_out)[0]
     return y.transpose(1, 2).unflatten(2, (x.shape[2], x.shape[3])) if tokens_out else y
+
+
+# ---- BatchNorm2d with batch statistics (+ GELU) in grad mode (include/dfx_fused.h, csrc/batchnorm_train.hip) --------------------
+BN_CHUNK_PIXELS = 8192      # DFX_BN_CHUNK_PIXELS of include/dfx_fused.h
+
+
+def _bn_partials(N, HW):
+    """chunks of all images of one channel: the workspace holds 6 (forward) / 8 (backward) floats per channel and chunk"""
+    return N * (-(-HW // BN_CHUNK_PIXELS))
+
+
+def batch_norm_train_forward(x, weight, bias, running_mean=None, running_var=None, momentum=0.1, eps=1e-5, act=None):
+    """-> (y, stats): y = act(batch_norm(x)) with the statistics of this batch, act None or "gelu"; stats [2C] fp32, the
+    batch mean [C] followed by 1 / sqrt(biased var + eps) [C], as ``batch_norm_backward`` reads them.  x [N,C,H,W] contiguous
+    fp32 with more than one value per channel.  running_mean / running_var (each may be None) are updated IN PLACE by the
+    kernel as nn.BatchNorm2d updates them (the unbiased variance, ``momentum`` a float) and their version counters moved, so
+    that ``models.fused.derived_key`` sees it; ``num_batches_tracked`` is the caller's."""
+    named = [("x", x), ("weight", weight), ("bias", bias)]
+    named += [(n, t) for n, t in (("running_mean", running_mean), ("running_var", running_var)) if t is not None]
+    _check_inputs(named)
+    _require(act in (None, "none", "gelu"), "batch_norm_train: act is None or 'gelu'")
+    _require(x.dim() == 4 and all(t.dtype == torch.float32 for _, t in named) and all(t.numel() == x.shape[1] for _, t in named[1:]),
+             "batch_norm_train: fp32, x [N,C,H,W], parameters and running statistics [C]")
+    N, C, H, W = x.shape
+    dev = x.device
+    y = torch.empty_like(x)
+    stats = torch.empty((2 * C,), dtype=torch.float32, device=dev)
+    ws = torch.empty((6 * C * _bn_partials(N, H * W),), dtype=torch.float32, device=dev)
+    _call("batch_norm_train", "dfx_batch_norm_train_f32", dev, x.data_ptr(), weight.data_ptr(), bias.data_ptr(), _ptr(running_mean),
+          _ptr(running_var), y.data_ptr(), stats.data_ptr(), ws.data_ptr(), N, C, H * W, float(eps), float(momentum), ACT[act])
+    for t in (running_mean, running_var):
+        if t is not None:
+            torch.autograd.graph.increment_version(t)
+    return y, stats
+
+
+def batch_norm_backward(grad_out, x, stats, weight, bias, eps=1e-5, act=None, need_x=True, need_gamma=True, need_beta=True):
+    """Gradients of ``batch_norm_train_forward``: -> (grad_x | None, grad_gamma | None, grad_beta | None), fp32, fresh tensors
+    (include/dfx_fused.h, dfx_batch_norm_backward_f32: two streaming launches, no atomics, the same bits every call).
+    grad_out and x [N,C,H,W] contiguous, stats [2C] as the forward wrote them, weight and bias [C], the forward's eps; with
+    act "gelu" the GELU's argument is recomputed from x: nothing else of the forward is needed."""
+    _check_inputs([("grad_out", grad_out), ("x", x), ("stats", stats), ("weight", weight), ("bias", bias)])
+    _require(act in (None, "none", "gelu"), "batch_norm_backward: act is None or 'gelu'")
+    _require(x.dim() == 4 and grad_out.shape == x.shape and grad_out.dtype == torch.float32 and x.dtype == torch.float32
+             and stats.dtype == torch.float32 and weight.dtype == torch.float32 and bias.dtype == torch.float32
+             and weight.numel() == x.shape[1] and bias.numel() == x.shape[1] and stats.numel() == 2 * x.shape[1],
+             "batch_norm_backward: fp32, grad_out and x [N,C,H,W], weight and bias [C], stats [2C]")
+    N, C, H, W = x.shape
+    dev = x.device
+    grad_x = torch.empty_like(x) if need_x else None
+    grad_gamma = torch.empty((C,), dtype=torch.float32, device=dev) if need_gamma else None
+    grad_beta = torch.empty((C,), dtype=torch.float32, device=dev) if need_beta else None
+    if need_x or need_gamma or need_beta:
+        ws = torch.empty((8 * C * _bn_partials(N, H * W),), dtype=torch.float32, device=dev)
+        _call("batch_norm_backward", "dfx_batch_norm_backward_f32", dev, grad_out.data_ptr(), x.data_ptr(), stats.data_ptr(),
+              weight.data_ptr(), bias.data_ptr(), _ptr(grad_x), _ptr(grad_gamma), _ptr(grad_beta), ws.data_ptr(), N, C, H * W, float(eps), ACT[act])
+    return grad_x, grad_gamma, grad_beta
+
+
+class _BatchNormFunction(torch.autograd.Function):
+    """apply(x, weight, bias, running_mean | None, running_var | None, momentum, eps, act) -> (y, the running buffers that were
+    given); keeps x and stats (and the two parameters, which are inputs) for the backward - neither the BatchNorm output nor
+    the GELU output."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, running_mean, running_var, momentum, eps, act):
+        y, stats = batch_norm_train_forward(x, weight, bias, running_mean, running_var, momentum, eps, act)
+        ctx.save_for_backward(x, stats, weight, bias)
+        ctx.eps, ctx.act = eps, act
+        # the running buffers are inputs written in place: declared dirty (and so returned), never differentiated
+        buffers = tuple(t for t in (running_mean, running_var) if t is not None)
+        if buffers:
+            ctx.mark_dirty(*buffers)
+            ctx.mark_non_differentiable(*buffers)
+        return (y,) + buffers
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output, *_buffers):
+        x, stats, weight, bias = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        # (looked up at call time: tests wrap it)
+        gx, gg, gb = batch_norm_backward(grad_output.contiguous(), x, stats, weight, bias, ctx.eps, ctx.act, need_x=need[0], need_gamma=need[1],
+                                         need_beta=need[2])
+        return gx, gg, gb, None, None, None, None, None
+
+
+def batch_norm_train_supported(bn):
+    """Is ``bn`` a BatchNorm the kernels cover: nn.BatchNorm2d in training mode (batch statistics), affine, a float momentum"""
+    return (type(bn) is torch.nn.BatchNorm2d and bn.training and bn.affine and isinstance(bn.momentum, float)
+            and 0.0 <= bn.momentum <= 1.0 and bn.weight.dtype == torch.float32)
+
+
+def batch_norm_train(x, bn, act=None):
+    """``bn(x)`` of an nn.BatchNorm2d in training mode (``batch_norm_train_supported``), followed by nn.GELU() when act is
+    "gelu", in three streaming launches; running statistics and ``num_batches_tracked`` move as the module moves them.  With
+    grad mode on and x or a parameter requiring a gradient the result carries an autograd node whose backward is
+    ``batch_norm_backward`` (computed for exactly the inputs that ask); otherwise no node is made."""
+    _require(batch_norm_train_supported(bn), "batch_norm_train: an affine nn.BatchNorm2d in training mode with a float momentum")
+    track = bn.track_running_stats and bn.running_mean is not None
+    rm, rv = (bn.running_mean, bn.running_var) if track else (None, None)
+    x = x.contiguous()
+    if torch.is_grad_enabled() and (x.requires_grad or bn.weight.requires_grad or bn.bias.requires_grad):
+        y = _BatchNormFunction.apply(x, bn.weight, bn.bias, rm, rv, float(bn.momentum), float(bn.eps), act)[0]
+    else:
+        y = batch_norm_train_forward(x, bn.weight, bn.bias, rm, rv, bn.momentum, bn.eps, act)[0]
+    if track and bn.num_batches_tracked is not None:
+        bn.num_batches_tracked.add_(1)
+    return y

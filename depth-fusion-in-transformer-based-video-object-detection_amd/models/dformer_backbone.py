@@ -3,7 +3,8 @@
   stem   conv3x3/s2 (1->16) + BN + GELU + conv3x3/s2 (16->32) + BN
   then   BN + conv3x3/s2 (32->64),  BN + conv3x3/s2 (64->128),  [BN + conv3x3/s2 (128->256)]
 The last stage exists (checkpoint keys) but the forward skips it (ref :142).  BatchNorm layers
-are live nn.BatchNorm2d: running statistics in eval mode.
+are live nn.BatchNorm2d: running statistics in eval mode, batch statistics in train mode - there, with
+something to differentiate and models.fused.DFORMER_TRAIN on, on dfx.ops.batch_norm_train.
 """
 import os
 from typing import Dict, List
@@ -16,7 +17,8 @@ from dfx import ops as _ops
 from util.memo import memo_on
 from util.misc import NestedTensor
 
-from .fused import derived_key, needs_grad
+from . import fused as _fused
+from .fused import derived_key, has_hooks, needs_grad
 from .position_encoding import build_position_encoding
 
 
@@ -43,6 +45,40 @@ class DownsamplePath(nn.Module):
             for p in layer.parameters():
                 p.requires_grad = False
         return layer
+
+
+def _train_route_usable(stages, x):
+    """May the stages' BatchNorms run on dfx.ops.batch_norm_train for this input?  Only as the DFORMER_TRAIN comment of
+    models/fused.py says; the per-layer conditions are ``_bn_train_usable``'s.  (Switch and size rule are read at call time.)"""
+    return (_fused.DFORMER_TRAIN and x.is_cuda and x.dtype == torch.float32 and not torch.is_autocast_enabled()
+            and needs_grad(stages, x))
+
+
+def _bn_train_usable(bn, x, gelu=False):
+    """``gelu``: the nn.GELU behind ``bn`` would run inside the same call (its own, smaller, measured size rule)"""
+    least = _fused.DFORMER_TRAIN_MIN_PIXELS_GELU if gelu else _fused.DFORMER_TRAIN_MIN_PIXELS
+    return (_ops.batch_norm_train_supported(bn) and not has_hooks(bn) and x.dim() == 4 and x.dtype == torch.float32
+            and bn.weight.device == x.device and x.shape[1] == bn.num_features
+            and x.shape[0] * x.shape[2] * x.shape[3] >= max(2, least))
+
+
+def _run_stage_train(stage, x):
+    """One stage of the stem in grad mode: every BatchNorm in training mode that the kernels cover runs as
+    dfx.ops.batch_norm_train (csrc/batchnorm_train.hip), with the nn.GELU that follows it inside the same call; every
+    other module - the convolutions, a BatchNorm in eval mode, one with hooks, a map below the size rule - is called as it is."""
+    mods = list(stage)
+    i = 0
+    while i < len(mods):
+        mod = mods[i]
+        nxt = mods[i + 1] if i + 1 < len(mods) else None
+        gelu = type(nxt) is nn.GELU and nxt.approximate == "none" and not has_hooks(nxt)
+        if isinstance(mod, nn.BatchNorm2d) and _bn_train_usable(mod, x, gelu):
+            x = _ops.batch_norm_train(x, mod, "gelu" if gelu else None)
+            i += 1 + int(gelu)
+        else:
+            x = mod(x)
+            i += 1
+    return x
 
 
 def _resize_mask(m, size):
@@ -85,8 +121,9 @@ class DFormerBackbone(nn.Module):
             x = self._forward_folded(stages, x)
             out["0"] = NestedTensor(x, _resize_mask(m, x.shape[-2:]))
             return out
+        train_route = _train_route_usable(stages, x)
         for i, stage in enumerate(stages):
-            x = stage(x)
+            x = _run_stage_train(stage, x) if train_route and not has_hooks(stage) else stage(x)
             if self.return_interm_layers:
                 out[str(i)] = NestedTensor(x, _resize_mask(m, x.shape[-2:]))
         if not self.return_interm_layers:

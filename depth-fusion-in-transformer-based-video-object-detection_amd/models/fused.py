@@ -50,6 +50,22 @@ ADDLN_TRAIN = os.environ.get("DFX_ADDLN_TRAIN", "1") != "0"
 # Python node costs more of it than the library's C++ nodes - so fewer rows keep the modules (tools/bench_addln_train.py,
 # profiles/r17_addln_train.txt).
 ADDLN_TRAIN_MIN_ROWS = 32 * 4200
+# The BatchNorms of the DFormer depth stem (models.dformer_backbone.DFormerBackbone) in grad mode on dfx.ops.batch_norm_train
+# (csrc/batchnorm_train.hip: batch statistics, the GELU of stage 0 inside the same call, three forward and two backward launches)
+# instead of nn.BatchNorm2d + nn.GELU under autograd; DFX_DFORMER_TRAIN=0 keeps the modules everywhere (A/B measurements).  Read
+# once at import.  Taken per layer for fp32 GPU tensors outside autocast when something needs a gradient, the BatchNorm is in
+# training mode, affine, with a float momentum and without hooks.  The stem's convolutions stay nn.Conv2d.
+DFORMER_TRAIN = os.environ.get("DFX_DFORMER_TRAIN", "1") != "0"
+# The smallest BatchNorm input (images x H x W pixels) at which one layer, forward + backward, MEASURED faster than the parent
+# commit's modules beyond the repetition spread (tools/bench_dformer_train.py, profiles/r18_dformer_train.txt).
+# A call costs 0.115 ms whatever its size - five short launches issued from Python - and the library's nodes cost 0.07-0.09 ms:
+#   BatchNorm alone: 534400 pixels (8 x 200 x 334 at 32 channels 1.83x, 32 x 100 x 167 at 64 channels 1.97x); 267200 pixels tie
+#     (1.07x inside the spread) and 133600 and fewer are 17-45 % SLOWER, so they keep the module;
+#   BatchNorm + GELU in one call (stage 0, 16 channels): 533600 pixels = two 400 x 667 maps (alone 2.91x, 32 maps 6.97x; the stem
+#     with this layer routed 1.28x at 2 frames).  One map wins alone (1.44x) but LOSES inside the stem (0.77x): a one-frame
+#     step is host-bound, and the node's host time shows there in full.  So one map keeps the modules.
+DFORMER_TRAIN_MIN_PIXELS = 8 * 200 * 334
+DFORMER_TRAIN_MIN_PIXELS_GELU = 2 * 400 * 667
 
 
 def derived_key(*sources):

@@ -106,6 +106,51 @@ int dfx_group_norm_backward_f32(const float *dy, const float *x, const float *st
                                 float *dx, float *dgamma, float *dbeta, float *workspace,
                                 int N, int C, long HW, int groups, int dy_tokens, void *stream);
 
+/* nn.BatchNorm2d in training mode (batch statistics), optionally followed by the exact GELU, of the DFormer depth stem
+ * (csrc/batchnorm_train.hip; the reference runs nn.BatchNorm2d and nn.GELU op by op, models/dformer_backbone.py):
+ *   mean[c], var[c]  over the N * HW values of channel c, var biased (divided by N * HW)
+ *   y = act(gamma[c] * (x - mean[c]) * rstd[c] + beta[c]),  rstd = 1 / sqrt(var + eps),  act DFX_ACT_NONE or DFX_ACT_GELU
+ *   stats [2C]: mean[0..C), rstd[C..2C) - what the backward reads
+ *   running_mean / running_var [C] (each may be NULL): r = (1 - momentum) * r + momentum * stat (formed in fp64 from the merged
+ *     statistics, rounded once), with the UNBIASED variance
+ *     (divided by N * HW - 1) for running_var, as nn.BatchNorm2d does; num_batches_tracked is the caller's
+ *   x, y [N,C,HW] packed NCHW (y may be NULL: statistics only); gamma, beta [C]
+ *   workspace: 6 * C * N * DFX_BN_CHUNKS(HW) floats (used as doubles: 8-byte aligned), caller-owned
+ * Every (image, channel) plane is cut into chunks of DFX_BN_CHUNK_PIXELS pixels, one workgroup each - the grid is a function
+ * of the shape alone.  A chunk is read once into registers: its mean relative to its first pixel, then its centred second
+ * moment, summed in fp64 (never E[x^2] - E[x]^2: the variance survives |mean| >> std); one thread per channel merges the
+ * chunks' (count, mean, M2) in ascending (image, chunk) order (Chan et al.), in fp64; mean and rstd are rounded to fp32
+ * once.  Accesses are 16 bytes wide when HW % 4 == 0 and x, y are 16-byte aligned, else 4.  No atomics: two calls give the
+ * same bits.  Three launches (two without y).
+ * Every check runs before the first launch: dimensions positive, N * HW >= 2 (as torch: more than one value per channel),
+ * N, C <= 65535, HW < 2^31 - DFX_BN_CHUNK_PIXELS, eps >= 0, 0 <= momentum <= 1. */
+#define DFX_BN_CHUNK_PIXELS 8192
+#define DFX_BN_CHUNKS(HW) (((HW) + DFX_BN_CHUNK_PIXELS - 1) / DFX_BN_CHUNK_PIXELS)
+int dfx_batch_norm_train_f32(const float *x, const float *gamma, const float *beta, float *running_mean,
+                             float *running_var, float *y, float *stats, float *workspace, int N, int C, long HW,
+                             double eps, double momentum, int act, void *stream);
+
+/* Backward of dfx_batch_norm_train_f32 from x and the ``stats`` it left (and the forward's eps); neither the BatchNorm output nor
+ * the GELU output is needed.  With xh = (x - mean) * rstd, z = gamma * xh + beta and g = dy (act none) or dy * gelu'(z)
+ * (DFX_ACT_GELU, z as the forward formed it from ``stats``), m = N * HW:
+ *   dx        = gamma * rstd * (g - sum g / m - xh * sum (g xh) / m)    [N,C,HW]
+ *   dgamma[c] = sum g * xh,   dbeta[c] = sum g                           [C]
+ * Each of the three outputs may be NULL and its work is then skipped (all NULL: DFX_OK without a launch); the others are
+ * overwritten with plain stores, never accumulated into.  workspace: 8 * C * N * DFX_BN_CHUNKS(HW) floats (used as doubles:
+ * 8-byte aligned), caller-owned.
+ * Two launches: per group of DFX_BN_BWD_GROUP(P) consecutive chunks (the forward's chunks, P = N * DFX_BN_CHUNKS(HW) per channel
+ * in (image, chunk) order; at most DFX_BN_BWD_MAX_GROUPS groups per channel) the fp64 sums of g, g u, u and u^2 with
+ * u = x - mean[c], then - per workgroup of one chunk - the channel's group sums added by one wave (lane l adds groups l and
+ * l + 64 in ascending order, then a shuffle butterfly),
+ * the batch statistics formed from them again in fp64 (dx does not inherit the rounding of ``stats`` to fp32: with few values
+ * per channel the three terms of dx cancel to eps / var of their size) and the chunk's dx in one pass, rounded to fp32 once.
+ * No atomics, the same bits every call.  Checks as the forward, before any launch. */
+#define DFX_BN_BWD_MAX_GROUPS 128
+#define DFX_BN_BWD_GROUP(P) (((P) + DFX_BN_BWD_MAX_GROUPS - 1) / DFX_BN_BWD_MAX_GROUPS)
+int dfx_batch_norm_backward_f32(const float *dy, const float *x, const float *stats, const float *gamma,
+                                const float *beta, float *dx, float *dgamma, float *dbeta, float *workspace, int N,
+                                int C, long HW, double eps, int act, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
