@@ -645,7 +645,10 @@ def roi_align(inp, rois, output_size, spatial_scale, sampling_ratio, aligned=Tru
 def bias_act_(x, bias, residual=None, relu=True):
     """In place on ``x`` [N,C,*spatial] (contiguous NCHW): x = relu?(x + bias[c] (+ residual)).
     One HBM pass for what the reference runs as FrozenBatchNorm2d (after folding its scale into
-    the convolution weights) + residual add + ReLU (include/dfx_fused.h)."""
+    the convolution weights) + residual add + ReLU (include/dfx_fused.h).
+    The arithmetic is (x + b) + r in fp32, then fmaxf(., 0): finite and infinite values come out bit-equal to that
+    expression in torch.  A NaN does not: fmaxf returns its other operand, so with ``relu`` a NaN element becomes 0
+    where torch.relu would keep it; without ``relu`` it stays NaN."""
     named = [("x", x), ("bias", bias)] + ([("residual", residual)] if residual is not None else [])
     _check_inputs(named)
     _require(x.dtype == torch.float32 and bias.dtype == torch.float32, "bias_act_ is implemented for float32")
