@@ -46,12 +46,7 @@ __device__ __forceinline__ void st(float *p, const float (&v)[W])
     else p[0] = v[0];
 }
 
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
+using dfx::wave_sum;
 
 // the four waves' sums added in wave order; every thread gets the result
 __device__ __forceinline__ double block_sum(double v, double *sh)
@@ -63,6 +58,8 @@ __device__ __forceinline__ double block_sum(double v, double *sh)
     return ((sh[0] + sh[1]) + sh[2]) + sh[3];
 }
 
+// the exact GELU, as activate() of mfma_tile.h states it: behind one shared function either the convolutions' code or
+// bn_apply's comes out different (profiles/r19_kernel_twins.txt), so the line stands twice
 __device__ __forceinline__ float gelu(float z) { return 0.5f * z * (1.f + erff(z * 0.70710678118654752440f)); }
 
 // d/dz of the exact GELU: Phi(z) + z * phi(z)

@@ -51,6 +51,26 @@ __device__ __forceinline__ int xcd_remap(int b, int nblk)
 
 constexpr int kWave = 64;
 
+// ---- lane reductions ---------------------------------------------------------------------
+// sum over the 64 lanes of a wave by an xor butterfly (all 64 get the result); float and double
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// sum over the 16 lanes of an aligned 16-lane group (all 16 get the result)
+__device__ __forceinline__ float sum16(float v)
+{
+    v += __shfl_xor(v, 8);
+    v += __shfl_xor(v, 4);
+    v += __shfl_xor(v, 2);
+    v += __shfl_xor(v, 1);
+    return v;
+}
+
 // ---- tuning / diagnostic knobs ----------------------------------------------------------------
 // Every DFX_* environment switch of the launchers (INTEGRATION.md "Diagnostic environment variables"), read ONCE per
 // process - a launch costs no getenv() scan and never races a setenv() - and again only on dfx_tuning_reload()

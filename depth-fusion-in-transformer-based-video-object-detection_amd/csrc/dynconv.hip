@@ -26,15 +26,7 @@ constexpr int X_F4 = (49 * C / 4 + 255) / 256; // float4 per thread for an X of 
 constexpr int X_F4_MAX = RP * C / 4 / 256;     //                                up to 64 rows (16)
 constexpr int K_F4 = C * DD / 4 / 256;         // float4 per thread for K1 or K2 (16)
 
-// sum over the 16 lanes of an aligned 16-lane group (all 16 get the result)
-__device__ __forceinline__ float sum16(float v)
-{
-    v += __shfl_xor(v, 8);
-    v += __shfl_xor(v, 4);
-    v += __shfl_xor(v, 2);
-    v += __shfl_xor(v, 1);
-    return v;
-}
+using dfx::sum16;
 
 template <int XF>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void dynamic_conv(const float *__restrict__ feats, const float *__restrict__ params,

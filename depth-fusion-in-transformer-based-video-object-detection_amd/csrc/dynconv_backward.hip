@@ -37,14 +37,7 @@ constexpr int X_F4_MAX = RP * C / 4 / 256;
 constexpr int K_F4 = C * DD / 4 / 256;
 constexpr int LN_FLOATS = 2 * DD + 2 * C;
 
-__device__ __forceinline__ float sum16(float v)
-{
-    v += __shfl_xor(v, 8);
-    v += __shfl_xor(v, 4);
-    v += __shfl_xor(v, 2);
-    v += __shfl_xor(v, 1);
-    return v;
-}
+using dfx::sum16;
 
 #define MFMA(A, B, ACC) ACC = __builtin_amdgcn_mfma_f32_32x32x2f32(A, B, ACC, 0, 0, 0)
 // row of accumulator register r inside a 32 x 32 tile

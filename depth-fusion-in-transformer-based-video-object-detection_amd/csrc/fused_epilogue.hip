@@ -1,7 +1,8 @@
 // Fused per-channel epilogues of the backbone convolutions (gfx950): one HBM pass instead of the
 // reference's mul + add (FrozenBatchNorm2d) + add (residual) + clamp (ReLU) kernels.
 // HBM-bound: 4 B read (+4 B residual) + 4 B written per element; 16-byte vector accesses, one
-// (image, channel) plane per workgroup row so the bias is a scalar.
+// (image, channel) plane per workgroup row so the bias is a scalar.  (The residual + LayerNorm tail of the transformer
+// sub-layers, dfx_add_layernorm_f32, is in layernorm_train.hip with its training form.)
 #include "dfx_common.h"
 #include "dfx_fused.h"
 
@@ -34,62 +35,6 @@ __global__ __launch_bounds__(256) void bias_act_nchw(const float *__restrict__ x
             if (RES) v += res[base + i];
             if (RELU) v = fmaxf(v, 0.f);
             out[base + i] = v;
-        }
-    }
-}
-
-// residual add + LayerNorm: one wave per row, the row lives in registers (<= 4 float4 per lane),
-// mean and variance by two in-register passes + xor-shuffle reductions (same formula as
-// nn.LayerNorm: biased variance, eps under the square root).
-template <int CHUNKS>
-__global__ __launch_bounds__(256) void add_layernorm(const float *__restrict__ x, const float *__restrict__ res,
-                                                     const float *__restrict__ gamma, const float *__restrict__ beta,
-                                                     float *__restrict__ out, long rows, int C, float eps)
-{
-    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const int lane = threadIdx.x & 63;
-    float4 v[CHUNKS];
-    float sum = 0.f;
-#pragma unroll
-    for (int k = 0; k < CHUNKS; ++k) {
-        const int c = k * 256 + lane * 4;
-        v[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (c < C) {
-            v[k] = *reinterpret_cast<const float4 *>(x + row * C + c);
-            if (res) {
-                const float4 r = *reinterpret_cast<const float4 *>(res + row * C + c);
-                v[k].x += r.x; v[k].y += r.y; v[k].z += r.z; v[k].w += r.w;
-            }
-            sum += (v[k].x + v[k].y) + (v[k].z + v[k].w);
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
-    const float mean = sum / (float)C;
-    float sq = 0.f;
-#pragma unroll
-    for (int k = 0; k < CHUNKS; ++k) {
-        if (k * 256 + lane * 4 < C) {
-            const float a = v[k].x - mean, b = v[k].y - mean, c2 = v[k].z - mean, d = v[k].w - mean;
-            sq += (a * a + b * b) + (c2 * c2 + d * d);
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o, 64);
-    const float rstd = rsqrtf(sq / (float)C + eps);
-#pragma unroll
-    for (int k = 0; k < CHUNKS; ++k) {
-        const int c = k * 256 + lane * 4;
-        if (c < C) {
-            const float4 g = *reinterpret_cast<const float4 *>(gamma + c);
-            const float4 b = *reinterpret_cast<const float4 *>(beta + c);
-            float4 o;
-            o.x = (v[k].x - mean) * rstd * g.x + b.x;
-            o.y = (v[k].y - mean) * rstd * g.y + b.y;
-            o.z = (v[k].z - mean) * rstd * g.z + b.z;
-            o.w = (v[k].w - mean) * rstd * g.w + b.w;
-            *reinterpret_cast<float4 *>(out + row * C + c) = o;
         }
     }
 }
@@ -191,25 +136,6 @@ extern "C" int dfx_box_refine_f32(const float *delta, const float *ref, int ref_
     hipLaunchKernelGGL(box_refine, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
                        reinterpret_cast<const float4 *>(delta), ref, ref_dim, reinterpret_cast<float4 *>(out), rows, eps);
     return dfx::check_launch("box_refine");
-}
-
-extern "C" int dfx_add_layernorm_f32(const float *x, const float *res, const float *gamma, const float *beta,
-                                     float *out, long rows, int C, float eps, void *stream)
-{
-    if (rows < 0 || C <= 0) return dfx::fail(DFX_EINVAL, "add_layernorm: bad dimension");
-    if (rows == 0) return DFX_OK;
-    if (!x || !gamma || !beta || !out) return dfx::fail(DFX_EINVAL, "add_layernorm: null pointer");
-    if ((C & 3) || C > 1024 || !dfx::aligned16(x) || !dfx::aligned16(out) || !dfx::aligned16(gamma) ||
-        !dfx::aligned16(beta) || (res && !dfx::aligned16(res)))
-        return dfx::fail(DFX_EINVAL, "add_layernorm: C must be a multiple of 4 and <= 1024, buffers 16-byte aligned");
-    if ((rows + 3) / 4 >= (1L << 31)) return dfx::fail(DFX_ERANGE, "add_layernorm: too many rows");
-    const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int chunks = (C + 255) / 256;
-    if (chunks == 1) hipLaunchKernelGGL(add_layernorm<1>, grid, block, 0, st, x, res, gamma, beta, out, rows, C, eps);
-    else if (chunks == 2) hipLaunchKernelGGL(add_layernorm<2>, grid, block, 0, st, x, res, gamma, beta, out, rows, C, eps);
-    else hipLaunchKernelGGL(add_layernorm<4>, grid, block, 0, st, x, res, gamma, beta, out, rows, C, eps);
-    return dfx::check_launch("add_layernorm");
 }
 
 extern "C" int dfx_bias_act_nchw_f32(const float *x, const float *bias, const float *residual, float *out, int N,

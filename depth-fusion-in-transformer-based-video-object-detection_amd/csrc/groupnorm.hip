@@ -13,12 +13,7 @@
 
 namespace {
 
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
+using dfx::wave_sum;
 
 __device__ __forceinline__ float block_sum(float v, float *red)
 {

@@ -20,12 +20,7 @@ namespace {
 
 constexpr int kChunks = DFX_GN_BWD_CHUNKS;
 
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
+using dfx::wave_sum;
 
 // ws[((n * chunks + chunk) * C + c) * 2] = sum over the chunk's pixels of dy, [.. + 1] = of dy * xh
 template <bool TOKENS>

@@ -1,7 +1,8 @@
-// The tail of every transformer sub-layer under a training step (gfx950):  out = LayerNorm(residual + dropout(x)).
-// Forward and backward on the decomposition of add_layernorm (csrc/fused_epilogue.hip): one wave per row, the row in
-// registers (<= 4 float4 per lane), xor-shuffle reductions, 16-byte accesses.  HBM-bound; algorithmic bytes per row of
-// C floats (DESIGN.md kernel table): forward 4C * (2 read + 2 written) + 8, with a mask 4C more read and C written;
+// The tail of every transformer sub-layer (gfx950):  out = LayerNorm(residual + dropout(x)).  One forward kernel behind the
+// inference entry (dfx_add_layernorm_f32) and the training entry (dfx_add_layernorm_train_f32), and the backward of the
+// latter, all on one decomposition: one wave per row, the row in registers (<= 4 float4 per lane), xor-shuffle
+// reductions, 16-byte accesses.  HBM-bound; algorithmic bytes per row of
+// C floats (DESIGN.md kernel table): training forward 4C * (2 read + 2 written) + 8, with a mask 4C more read and C written;
 // backward 4C * (2 read + 1 written) + 8, with a mask C more read and 4C more written.  No atomics anywhere: the
 // parameter gradients go through a [grid, 2C] workspace that a second launch adds up in a fixed order.
 #include "dfx_common.h"
@@ -18,22 +19,24 @@ __device__ __forceinline__ float mul_rounded(float a, float b)
     return p;
 }
 
-// Forward: s = res + x * mask, out = LN(s) with add_layernorm's arithmetic in add_layernorm's order; s, mean, rstd and
-// (with a mask) one keep byte per element are what the backward reads.
-// ``out`` must have add_layernorm's BITS, so which products are fused into an fma cannot be left to the compiler here (it
-// decides per kernel: the same source line came out fused in one of the two and unfused in the other).  Contraction is off
-// in this kernel and every fma is written out as the compiled add_layernorm<CHUNKS> has it (read from its ISA):
+// Forward, both entries: v = res + x (* mask), out = LN(v): mean and variance by two in-register passes (nn.LayerNorm's
+// formula: biased variance, eps under the square root).  TRAIN adds what the backward reads: s = v, mean, rstd and (with a
+// mask) one keep byte per element; TRAIN = false touches none of mask, s, mean_out, rstd_out and keep.
+// The arithmetic of dfx_add_layernorm_f32 and of dfx_add_layernorm_train_f32 is this one source, with contraction off: which
+// products are fused into an fma is written out, not left to the compiler (which decides per kernel).  The placement is
+// frozen because it is today's bits, those of every trained checkpoint's inference tail:
 //   variance, 1 chunk:       (a a + b b) + (c c + d d), no fma
 //   variance, 2 or 4 chunks: fma(a, a, b b) + fma(c, c, d d)
 //   result:                  fma((v - mean) rstd, gamma, beta)
-// tests/test_addln_train_gpu.py compares the bits for every chunk count and is what notices a compiler that decides otherwise.
-template <int CHUNKS>
-__global__ __launch_bounds__(256) void add_layernorm_train(const float *__restrict__ x, const float *__restrict__ res,
-                                                           const float *__restrict__ mask, const float *__restrict__ gamma,
-                                                           const float *__restrict__ beta, float *__restrict__ out,
-                                                           float *__restrict__ s, float *__restrict__ mean_out,
-                                                           float *__restrict__ rstd_out, unsigned char *__restrict__ keep,
-                                                           long rows, int C, float eps)
+// tests/test_addln_train_gpu.py's torch.equal between the two entries therefore checks the contract of the C ABI (same
+// inputs, same ``out``), not one kernel's transcription of the other.
+template <int CHUNKS, bool TRAIN>
+__global__ __launch_bounds__(256) void add_layernorm(const float *__restrict__ x, const float *__restrict__ res,
+                                                     const float *__restrict__ mask, const float *__restrict__ gamma,
+                                                     const float *__restrict__ beta, float *__restrict__ out,
+                                                     float *__restrict__ s, float *__restrict__ mean_out,
+                                                     float *__restrict__ rstd_out, unsigned char *__restrict__ keep,
+                                                     long rows, int C, float eps)
 {
 #pragma clang fp contract(off)
     const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -47,7 +50,7 @@ __global__ __launch_bounds__(256) void add_layernorm_train(const float *__restri
         v[k] = make_float4(0.f, 0.f, 0.f, 0.f);
         if (c < C) {
             v[k] = *reinterpret_cast<const float4 *>(x + row * C + c);
-            if (mask) {
+            if (TRAIN && mask) {
                 const float4 m = *reinterpret_cast<const float4 *>(mask + row * C + c);
                 v[k].x = mul_rounded(v[k].x, m.x); v[k].y = mul_rounded(v[k].y, m.y);
                 v[k].z = mul_rounded(v[k].z, m.z); v[k].w = mul_rounded(v[k].w, m.w);
@@ -59,10 +62,11 @@ __global__ __launch_bounds__(256) void add_layernorm_train(const float *__restri
                 const float4 r = *reinterpret_cast<const float4 *>(res + row * C + c);
                 v[k].x += r.x; v[k].y += r.y; v[k].z += r.z; v[k].w += r.w;
             }
-            *reinterpret_cast<float4 *>(s + row * C + c) = v[k];
+            if (TRAIN) *reinterpret_cast<float4 *>(s + row * C + c) = v[k];
             sum += (v[k].x + v[k].y) + (v[k].z + v[k].w);
         }
     }
+    // (both butterflies stay open-coded: through dfx::wave_sum the TRAIN instantiations take 2 to 5 more VGPRs)
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
     const float mean = sum / (float)C;
@@ -78,9 +82,9 @@ __global__ __launch_bounds__(256) void add_layernorm_train(const float *__restri
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o, 64);
     const float rstd = rsqrtf(sq / (float)C + eps);
-    if (lane == 0) {
+    if (TRAIN && lane == 0) {
         // what the backward multiplies every xh by is the correctly rounded 1 / sqrt, not the approximate rsqrtf that
-        // ``out`` shares with the inference kernel (up to 1 ulp off, which would be an error of every gradient's row)
+        // ``out`` is made with (up to 1 ulp off, which would be an error of every gradient's row)
         mean_out[row] = mean;
         rstd_out[row] = 1.0f / sqrtf(sq / (float)C + eps);
     }
@@ -98,6 +102,25 @@ __global__ __launch_bounds__(256) void add_layernorm_train(const float *__restri
             *reinterpret_cast<float4 *>(out + row * C + c) = o;
         }
     }
+}
+
+// what both forward entries do once their arguments have passed: one wave per row, 4 rows per workgroup
+template <bool TRAIN>
+int launch_forward(const char *what, const float *x, const float *res, const float *mask, const float *gamma,
+                   const float *beta, float *out, float *s, float *mean, float *rstd, unsigned char *keep, long rows, int C,
+                   float eps, void *stream)
+{
+    if ((rows + 3) / 4 >= (1L << 31)) return dfx::fail(DFX_ERANGE, "%s: too many rows", what);
+    const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int chunks = (C + 255) / 256;
+#define DFX_GO(CH) \
+    hipLaunchKernelGGL((add_layernorm<CH, TRAIN>), grid, block, 0, st, x, res, mask, gamma, beta, out, s, mean, rstd, keep, rows, C, eps)
+    if (chunks == 1) DFX_GO(1);
+    else if (chunks == 2) DFX_GO(2);
+    else DFX_GO(4);
+#undef DFX_GO
+    return dfx::check_launch(what);
 }
 
 // Backward.  Wave w of workgroup b is wave b * 4 + w of 4 * gridDim.x; it walks rows w, w + waves, w + 2 waves, ... in
@@ -294,17 +317,20 @@ extern "C" int dfx_add_layernorm_train_f32(const float *x, const float *res, con
     if (!dfx::aligned16(x) || !dfx::aligned16(out) || !dfx::aligned16(s) || !dfx::aligned16(gamma) || !dfx::aligned16(beta) ||
         (res && !dfx::aligned16(res)) || (mask && (!dfx::aligned16(mask) || (reinterpret_cast<uintptr_t>(keep) & 3u))))
         return dfx::fail(DFX_EINVAL, "add_layernorm_train: buffers must be 16-byte aligned (keep: 4-byte)");
-    if ((rows + 3) / 4 >= (1L << 31)) return dfx::fail(DFX_ERANGE, "add_layernorm_train: too many rows");
-    const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int chunks = (C + 255) / 256;
-#define DFX_GO(CH) \
-    hipLaunchKernelGGL(add_layernorm_train<CH>, grid, block, 0, st, x, res, mask, gamma, beta, out, s, mean, rstd, keep, rows, C, eps)
-    if (chunks == 1) DFX_GO(1);
-    else if (chunks == 2) DFX_GO(2);
-    else DFX_GO(4);
-#undef DFX_GO
-    return dfx::check_launch("add_layernorm_train");
+    return launch_forward<true>("add_layernorm_train", x, res, mask, gamma, beta, out, s, mean, rstd, keep, rows, C, eps, stream);
+}
+
+// the inference tail (include/dfx_fused.h): the same kernel without what only the backward reads
+extern "C" int dfx_add_layernorm_f32(const float *x, const float *res, const float *gamma, const float *beta,
+                                     float *out, long rows, int C, float eps, void *stream)
+{
+    if (rows < 0 || C <= 0) return dfx::fail(DFX_EINVAL, "add_layernorm: bad dimension");
+    if (rows == 0) return DFX_OK;
+    if (!x || !gamma || !beta || !out) return dfx::fail(DFX_EINVAL, "add_layernorm: null pointer");
+    if ((C & 3) || C > 1024 || !dfx::aligned16(x) || !dfx::aligned16(out) || !dfx::aligned16(gamma) ||
+        !dfx::aligned16(beta) || (res && !dfx::aligned16(res)))
+        return dfx::fail(DFX_EINVAL, "add_layernorm: C must be a multiple of 4 and <= 1024, buffers 16-byte aligned");
+    return launch_forward<false>("add_layernorm", x, res, nullptr, gamma, beta, out, nullptr, nullptr, nullptr, nullptr, rows, C, eps, stream);
 }
 
 extern "C" int dfx_add_layernorm_backward_f32(const float *dy, const float *s, const float *mean, const float *rstd,

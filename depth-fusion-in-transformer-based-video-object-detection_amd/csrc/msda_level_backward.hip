@@ -30,7 +30,7 @@
 // Not bit-reproducible in the default mode: the order in which the LDS adds of different lanes and waves retire is not
 // fixed, so two calls may differ in the last bits of grad_value - as the global-atomic route this replaces.  The three
 // small gradients come from msda_fused_bwd's NEED_VALUE = false instantiation and keep their bit-reproducibility.  The
-// deterministic mode runs msda_level_grad_value_fixed (below) instead: the same decomposition, sums in 64-bit fixed point.
+// deterministic mode runs the same kernel under its other accumulation policy (FixedSum below): sums in 64-bit fixed point.
 #include "dfx_common.h"
 #include "fixed_sum.h"
 #include "msda_level_taps.h"
@@ -42,181 +42,142 @@ using namespace dfx::level;
 struct GradValueArgs {
     const float *ref, *off, *logits, *grad_out;
     float *grad_value;
-    long off_pitch, logit_pitch;
-    int H, W, Lq, PL, nitems;
-};
-
-// the octet's 8 channels of one corner: token `d` of plane 0 and of plane 1 (`plane` floats further)
-__device__ __forceinline__ void add_corner(float *d, int plane, float w, const float4 &g0, const float4 &g1)
-{
-    atomicAdd(d, w * g0.x);
-    atomicAdd(d + 1, w * g0.y);
-    atomicAdd(d + 2, w * g0.z);
-    atomicAdd(d + 3, w * g0.w);
-    atomicAdd(d + plane, w * g1.x);
-    atomicAdd(d + plane + 1, w * g1.y);
-    atomicAdd(d + plane + 2, w * g1.z);
-    atomicAdd(d + plane + 3, w * g1.w);
-}
-
-template <int REFDIM>
-__global__ __launch_bounds__(THREADS) void msda_level_grad_value(const GradValueArgs g)
-{
-    const int H = g.H, W = g.W, Lq = g.Lq, PL = g.PL;
-    extern __shared__ float4 img[];                 // [2 planes][PL bordered tokens] of accumulators
-    const int tid = threadIdx.x;
-    const int S = H * W, WB = W + 2;
-    const Level lv = make_level(H, W);
-    float *org = reinterpret_cast<float *>(img + WB + 1);      // token (0, 0) of the map inside the bordered image
-    const int plane = 4 * PL, row = 4 * WB;
-    // the flush's walk: lane pair = (token, chunk); the thread's first token and the (row, column) step between its tokens
-    const int chunk = tid & 1, tok0_y = (tid >> 1) / W, tok0_x = (tid >> 1) - tok0_y * W;
-    const int step_y = (THREADS / 2) / W, step_x = (THREADS / 2) - step_y * W;
-
-    // item -> (frame, head, octet), the forward's order: item & 7 is the head, fixed per workgroup of the persistent grid
-    for (int item = blockIdx.x; item < g.nitems; item += (int)gridDim.x) {
-        const int head = item & 7, r = item >> 3;
-        const int n = r >> 2, oct = r & 3;
-        for (int j = tid; j < 2 * PL; j += THREADS) img[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-
-        const float *__restrict__ refn = g.ref + (long)n * Lq * REFDIM;
-        const float *__restrict__ offn = g.off + (long)n * Lq * g.off_pitch + head * 8;
-        const float *__restrict__ lgn = g.logits + (long)n * Lq * g.logit_pitch + head * 4;
-        const float *__restrict__ gon = g.grad_out + (long)n * Lq * 256 + head * 32 + oct * 8;
-        int q = tid;
-        bool have = q < Lq;
-        Raw raw;
-        float4 g0, g1;
-        if (have) {
-            raw = load_raw<REFDIM>(refn + (long)q * REFDIM, offn + q * g.off_pitch, lgn + q * g.logit_pitch);
-            g0 = *reinterpret_cast<const float4 *>(gon + (long)q * 256);
-            g1 = *reinterpret_cast<const float4 *>(gon + (long)q * 256 + 4);
-        }
-        __syncthreads();                            // the image is zero before the first add
-
-        while (have) {
-            const Taps tp = make_taps<REFDIM>(raw, lv);
-            const float4 c0 = g0, c1 = g1;
-            // the next query's operands load under this query's adds
-            q += THREADS;
-            have = q < Lq;
-            if (have) {
-                raw = load_raw<REFDIM>(refn + (long)q * REFDIM, offn + q * g.off_pitch, lgn + q * g.logit_pitch);
-                g0 = *reinterpret_cast<const float4 *>(gon + (long)q * 256);
-                g1 = *reinterpret_cast<const float4 *>(gon + (long)q * 256 + 4);
-            }
-#pragma unroll
-            for (int p = 0; p < 4; ++p) {
-                float *d = org + 4 * tp.tb[p];
-                add_corner(d, plane, tp.wt[p].x, c0, c1);
-                add_corner(d + 4, plane, tp.wt[p].y, c0, c1);
-                add_corner(d + row, plane, tp.wb[p].x, c0, c1);
-                add_corner(d + row + 4, plane, tp.wb[p].y, c0, c1);
-            }
-        }
-        __syncthreads();                            // every add of this item has landed
-
-        // ---- flush the interior: lane pair = (token, chunk), 32 contiguous bytes per token ----
-        float *__restrict__ gv = g.grad_value + (long)n * S * 256 + head * 32 + oct * 8;
-        // a thread's tokens are THREADS / 2 apart: (y, x) advance by (step_y, step_x) with one carry, no division per store
-        for (int tok = tid >> 1, y = tok0_y, x = tok0_x; tok < S; tok += THREADS / 2) {
-            *reinterpret_cast<float4 *>(gv + (long)tok * 256 + chunk * 4) = img[chunk * PL + (y + 1) * WB + x + 1];
-            x += step_x;
-            y += step_y;
-            if (x >= W) { x -= W; ++y; }
-        }
-        __syncthreads();                            // the flush has read the image before the next item zeroes it
-    }
-}
-
-// ---- the fixed-point twin (fixed_sum.h): the same decomposition with int64 accumulators ---------------------------------
-// item = one (frame, head, channel QUAD) over all queries of the frame, N * 64 items; the bordered image holds 4 x int64
-// per token (32 bytes, token-major: the image is as large as the float kernel's two planes of 16 bytes, so the same
-// levels fit), zeroed with 16-byte LDS writes.  Every query makes 16 corners x 4 channels return-less ds_add_u64 of
-// to_fixed(corner weight x attention weight x grad_out[c]), the float kernel's fp32 product.  The flush converts the
-// interior to fp32 and stores 16 bytes per token: one writer per element, zeros included.  A sum does not depend on the
-// order of its adds, so two calls - and calls on permuted queries - give the same bits.  Out-of-map corners add into the
-// border as above; whatever gathers there is never read.  item & 7 is the head as above, so the 8 quads of a (frame, head),
-// which read the same 128-byte grad_out rows, run next to each other.
-struct GradValueFixedArgs {
-    const float *ref, *off, *logits, *grad_out;
-    float *grad_value;
-    const void *scratch;
+    const void *scratch;        // FixedSum: the word enqueue_absmax leaves (fixed_sum.h); FloatSum: unused
     long off_pitch, logit_pitch;
     int H, W, Lq, PL, nitems, F;
 };
 
-__device__ __forceinline__ void add_corner_fixed(unsigned long long *d, float w, const float4 &g, double up)
-{
-    atomicAdd(d, dfx::fixed::to_fixed(w * g.x, up));
-    atomicAdd(d + 1, dfx::fixed::to_fixed(w * g.y, up));
-    atomicAdd(d + 2, dfx::fixed::to_fixed(w * g.z, up));
-    atomicAdd(d + 3, dfx::fixed::to_fixed(w * g.w, up));
-}
+// ---- the two accumulation policies ----------------------------------------------------------------------------------
+// A policy owns the channels of an item (CH), the accumulator type, where token (0, 0) of the map lies in the bordered
+// image, the add of one corner's CH channels, what the kernel derives once (Ctx), the 16 bytes a flush store writes and,
+// on the host, what its entry checks and enqueues ahead of the launch (prepare).
+// In both, token t's accumulators of a chunk start 4 * t accumulators after the origin, and out-of-map corners add into
+// the border, which is never flushed.
 
-template <int REFDIM>
-__global__ __launch_bounds__(THREADS) void msda_level_grad_value_fixed(const GradValueFixedArgs g)
+// fp32 sums, item = channel octet: two planes of 16-byte chunks (plane c = channels 4c .. 4c+3), PL tokens apart
+struct FloatSum {
+    static constexpr int CH = 8;
+    using Acc = float;
+    struct Ctx {
+        int plane;      // floats between a token's two chunks
+    };
+    static int prepare(const char *, const float *, long, void *, hipStream_t) { return DFX_OK; }
+    static __device__ __forceinline__ Ctx context(const GradValueArgs &g) { return {4 * g.PL}; }
+    static __device__ __forceinline__ Acc *origin(float4 *img, int WB) { return reinterpret_cast<Acc *>(img + WB + 1); }
+    static __device__ __forceinline__ void add(Acc *d, const Ctx &c, float w, const float4 (&g)[2])
+    {
+        atomicAdd(d, w * g[0].x);
+        atomicAdd(d + 1, w * g[0].y);
+        atomicAdd(d + 2, w * g[0].z);
+        atomicAdd(d + 3, w * g[0].w);
+        atomicAdd(d + c.plane, w * g[1].x);
+        atomicAdd(d + c.plane + 1, w * g[1].y);
+        atomicAdd(d + c.plane + 2, w * g[1].z);
+        atomicAdd(d + c.plane + 3, w * g[1].w);
+    }
+    // chunk `chunk` of bordered token `tok`
+    static __device__ __forceinline__ float4 flushed(const float4 *img, const Ctx &, int PL, int tok, int chunk)
+    {
+        return img[chunk * PL + tok];
+    }
+};
+
+// 64-bit fixed-point sums (fixed_sum.h), item = channel QUAD: 4 x int64 per token (32 bytes, token-major: the image is as
+// large as FloatSum's two planes of 16 bytes, so the same levels fit).  Every add is to_fixed of FloatSum's fp32 product, so
+// a sum does not depend on the order of its adds: two calls - and calls on permuted queries - give the same bits.
+struct FixedSum {
+    static constexpr int CH = 4;
+    using Acc = unsigned long long;
+    using Ctx = dfx::fixed::Scale;
+    // the launch's scale: max |grad_out| into the caller's scratch word, on the stream ahead of the kernel
+    static int prepare(const char *what, const float *grad_out, long n, void *scratch, hipStream_t st)
+    {
+        if (!scratch || !dfx::aligned16(scratch)) return dfx::fail(DFX_EINVAL, "%s: null or misaligned scratch word", what);
+        return dfx::fixed::enqueue_absmax(what, grad_out, n, scratch, st);
+    }
+    static __device__ __forceinline__ Ctx context(const GradValueArgs &g) { return dfx::fixed::load_scale(g.scratch, g.F); }
+    static __device__ __forceinline__ Acc *origin(float4 *img, int WB) { return reinterpret_cast<Acc *>(img + 2 * (WB + 1)); }
+    static __device__ __forceinline__ void add(Acc *d, const Ctx &sc, float w, const float4 (&g)[1])
+    {
+        atomicAdd(d, dfx::fixed::to_fixed(w * g[0].x, sc.up));
+        atomicAdd(d + 1, dfx::fixed::to_fixed(w * g[0].y, sc.up));
+        atomicAdd(d + 2, dfx::fixed::to_fixed(w * g[0].z, sc.up));
+        atomicAdd(d + 3, dfx::fixed::to_fixed(w * g[0].w, sc.up));
+    }
+    static __device__ __forceinline__ float4 flushed(const float4 *img, const Ctx &sc, int, int tok, int)
+    {
+        const longlong2 *sums = reinterpret_cast<const longlong2 *>(img);
+        const longlong2 a = sums[2 * tok], b = sums[2 * tok + 1];
+        return make_float4(dfx::fixed::from_fixed(a.x, sc), dfx::fixed::from_fixed(a.y, sc), dfx::fixed::from_fixed(b.x, sc),
+                           dfx::fixed::from_fixed(b.y, sc));
+    }
+};
+
+// item = one (frame, head, CH channels) over all queries of the frame: PARTS = 32 / CH items per (frame, head).  item & 7 is
+// the head, so the parts of a (frame, head), which read the same 128-byte grad_out rows, run next to each other.
+template <int REFDIM, typename SUM>
+__global__ __launch_bounds__(THREADS) void msda_level_grad_value(const GradValueArgs g)
 {
+    constexpr int CH = SUM::CH, PARTS = 32 / CH, NQ = CH / 4;      // NQ: float4 of grad_out per query = chunks per token
     const int H = g.H, W = g.W, Lq = g.Lq, PL = g.PL;
-    extern __shared__ float4 img[];                 // [PL bordered tokens][4 channels] of int64 accumulators: 2 * PL chunks
+    extern __shared__ float4 img[];                 // 2 * PL chunks of 16 bytes: the bordered image of accumulators
     const int tid = threadIdx.x;
     const int S = H * W, WB = W + 2;
     const Level lv = make_level(H, W);
-    unsigned long long *org = reinterpret_cast<unsigned long long *>(img + 2 * (WB + 1));      // token (0, 0) of the map
+    typename SUM::Acc *org = SUM::origin(img, WB);  // token (0, 0) of the map inside the bordered image
     const int row = 4 * WB;
-    const dfx::fixed::Scale sc = dfx::fixed::load_scale(g.scratch, g.F);
-    // the flush's walk: one token per thread; its first token and the (row, column) step between its tokens
-    const int tok0_y = tid / W, tok0_x = tid - tok0_y * W;
-    const int step_y = THREADS / W, step_x = THREADS - step_y * W;
+    const typename SUM::Ctx ctx = SUM::context(g);
+    // the flush's walk: NQ lanes = (token, chunk); the thread's first token and the (row, column) step between its tokens
+    const int chunk = tid & (NQ - 1), tok0_y = (tid / NQ) / W, tok0_x = (tid / NQ) - tok0_y * W;
+    const int step_y = (THREADS / NQ) / W, step_x = (THREADS / NQ) - step_y * W;
 
+    // item -> (frame, head, part), the forward's order: item & 7 is the head, fixed per workgroup of the persistent grid
     for (int item = blockIdx.x; item < g.nitems; item += (int)gridDim.x) {
         const int head = item & 7, r = item >> 3;
-        const int n = r >> 3, quad = r & 7;
+        const int n = r / PARTS, part = r & (PARTS - 1);
         for (int j = tid; j < 2 * PL; j += THREADS) img[j] = make_float4(0.f, 0.f, 0.f, 0.f);
 
         const float *__restrict__ refn = g.ref + (long)n * Lq * REFDIM;
         const float *__restrict__ offn = g.off + (long)n * Lq * g.off_pitch + head * 8;
         const float *__restrict__ lgn = g.logits + (long)n * Lq * g.logit_pitch + head * 4;
-        const float *__restrict__ gon = g.grad_out + (long)n * Lq * 256 + head * 32 + quad * 4;
+        const float *__restrict__ gon = g.grad_out + (long)n * Lq * 256 + head * 32 + part * CH;
         int q = tid;
         bool have = q < Lq;
         Raw raw;
-        float4 g0;
-        if (have) {
+        float4 go[NQ];
+        auto fetch = [&] {
             raw = load_raw<REFDIM>(refn + (long)q * REFDIM, offn + q * g.off_pitch, lgn + q * g.logit_pitch);
-            g0 = *reinterpret_cast<const float4 *>(gon + (long)q * 256);
-        }
+#pragma unroll
+            for (int k = 0; k < NQ; ++k) go[k] = *reinterpret_cast<const float4 *>(gon + (long)q * 256 + 4 * k);
+        };
+        if (have) fetch();
         __syncthreads();                            // the image is zero before the first add
 
         while (have) {
             const Taps tp = make_taps<REFDIM>(raw, lv);
-            const float4 c0 = g0;
+            float4 c[NQ];
+#pragma unroll
+            for (int k = 0; k < NQ; ++k) c[k] = go[k];
+            // the next query's operands load under this query's adds
             q += THREADS;
             have = q < Lq;
-            if (have) {
-                raw = load_raw<REFDIM>(refn + (long)q * REFDIM, offn + q * g.off_pitch, lgn + q * g.logit_pitch);
-                g0 = *reinterpret_cast<const float4 *>(gon + (long)q * 256);
-            }
+            if (have) fetch();
 #pragma unroll
             for (int p = 0; p < 4; ++p) {
-                unsigned long long *d = org + 4 * tp.tb[p];
-                add_corner_fixed(d, tp.wt[p].x, c0, sc.up);
-                add_corner_fixed(d + 4, tp.wt[p].y, c0, sc.up);
-                add_corner_fixed(d + row, tp.wb[p].x, c0, sc.up);
-                add_corner_fixed(d + row + 4, tp.wb[p].y, c0, sc.up);
+                typename SUM::Acc *d = org + 4 * tp.tb[p];
+                SUM::add(d, ctx, tp.wt[p].x, c);
+                SUM::add(d + 4, ctx, tp.wt[p].y, c);
+                SUM::add(d + row, ctx, tp.wb[p].x, c);
+                SUM::add(d + row + 4, ctx, tp.wb[p].y, c);
             }
         }
         __syncthreads();                            // every add of this item has landed
 
-        // ---- flush the interior: one token per thread, 4 sums -> 16 bytes of fp32 ----
-        float *__restrict__ gv = g.grad_value + (long)n * S * 256 + head * 32 + quad * 4;
-        const longlong2 *sums = reinterpret_cast<const longlong2 *>(img);
-        for (int tok = tid, y = tok0_y, x = tok0_x; tok < S; tok += THREADS) {
-            const int at = 2 * ((y + 1) * WB + x + 1);
-            const longlong2 a = sums[at], b = sums[at + 1];
-            *reinterpret_cast<float4 *>(gv + (long)tok * 256) =
-                make_float4(dfx::fixed::from_fixed(a.x, sc), dfx::fixed::from_fixed(a.y, sc), dfx::fixed::from_fixed(b.x, sc),
-                            dfx::fixed::from_fixed(b.y, sc));
+        // ---- flush the interior, zeros included: 16 bytes per (token, chunk), 4 * CH contiguous bytes per token ----
+        float *__restrict__ gv = g.grad_value + (long)n * S * 256 + head * 32 + part * CH;
+        // a thread's tokens are THREADS / NQ apart: (y, x) advance by (step_y, step_x) with one carry, no division per store
+        for (int tok = tid / NQ, y = tok0_y, x = tok0_x; tok < S; tok += THREADS / NQ) {
+            *reinterpret_cast<float4 *>(gv + (long)tok * 256 + chunk * 4) = SUM::flushed(img, ctx, PL, (y + 1) * WB + x + 1, chunk);
             x += step_x;
             y += step_y;
             if (x >= W) { x -= W; ++y; }
@@ -244,62 +205,52 @@ int check_level_args(const char *what, const float *ref, int ref_dim, const floa
     return DFX_OK;
 }
 
+// Both entry points: the argument rules, the policy's own preparation, the LDS opt-in, the persistent grid, the launch.
+template <typename SUM>
+int launch_grad_value(const char *what, const char *kernel, const float *ref, int ref_dim, const float *off, long off_pitch,
+                      const float *logits, long logit_pitch, const float *grad_out, int N, int H, int W, int Lq,
+                      float *grad_value, void *scratch, void *stream)
+{
+    if (N < 0 || H <= 0 || W <= 0 || Lq < 0) return dfx::fail(DFX_EINVAL, "%s: bad dimension", what);
+    if (N == 0) return DFX_OK;
+    if (const int rc = check_level_args(what, ref, ref_dim, off, off_pitch, logits, logit_pitch, grad_out, N, H, W, Lq, grad_value))
+        return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (const int rc = SUM::prepare(what, grad_out, (long)N * Lq * 256, scratch, st)) return rc;
+    const int PL = (int)plane_tokens(H, W);
+    const size_t lds = (size_t)2 * PL * 16;
+    if (const int rc = dfx::raise_lds_limit<&msda_level_grad_value<2, SUM>, &msda_level_grad_value<4, SUM>>(what, (int)LDS_CAP))
+        return rc;
+    const int nitems = N * 8 * (32 / SUM::CH);
+    const GradValueArgs g{ref, off, logits, grad_out, grad_value, scratch, off_pitch, logit_pitch, H, W, Lq, PL, nitems,
+                          dfx::fixed::fraction_bits(dfx::fixed::msda_terms(Lq))};
+    // persistent: at most one workgroup per CU, a multiple of 8 so that item & 7 (the head) is fixed per workgroup; the CU
+    // count is that of the device of the first call (as the forward's grid), the machines this runs on being uniform
+    static const int ncu = persistent_grid();
+    const int grid = nitems < ncu ? nitems : ncu;
+    const int S = H * W;
+    // algorithmic bytes of this launch: grad_out + offsets + logits + reference points read, grad_value written (every
+    // part of a head reads the head's offsets, logits and reference points again: not counted)
+    const long bytes = 4L * ((long)N * Lq * (256 + 64 + 32 + ref_dim) + (long)N * S * 256);
+    if (ref_dim == 2) dfx::launch_timed(bytes, Lq, S, msda_level_grad_value<2, SUM>, dim3((unsigned)grid), dim3(THREADS), lds, st, g);
+    else dfx::launch_timed(bytes, Lq, S, msda_level_grad_value<4, SUM>, dim3((unsigned)grid), dim3(THREADS), lds, st, g);
+    return dfx::check_launch(kernel);
+}
+
 }  // namespace
 
 extern "C" int dfx_msda_level_grad_value_fixed_f32(const float *ref, int ref_dim, const float *off, long off_pitch,
                                                    const float *logits, long logit_pitch, const float *grad_out, int N,
                                                    int H, int W, int Lq, float *grad_value, void *scratch, void *stream)
 {
-    const char *what = "msda level grad_value (fixed)";
-    if (N < 0 || H <= 0 || W <= 0 || Lq < 0) return dfx::fail(DFX_EINVAL, "%s: bad dimension", what);
-    if (N == 0) return DFX_OK;
-    if (!scratch || !dfx::aligned16(scratch)) return dfx::fail(DFX_EINVAL, "%s: null or misaligned scratch word", what);
-    if (const int rc = check_level_args(what, ref, ref_dim, off, off_pitch, logits, logit_pitch, grad_out, N, H, W, Lq, grad_value))
-        return rc;
-    const int PL = (int)plane_tokens(H, W);
-    const size_t lds = (size_t)2 * PL * 16;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (const int rc = dfx::raise_lds_limit<&msda_level_grad_value_fixed<2>, &msda_level_grad_value_fixed<4>>(what, (int)LDS_CAP))
-        return rc;
-    if (const int rc = dfx::fixed::enqueue_absmax(what, grad_out, (long)N * Lq * 256, scratch, st)) return rc;
-    const int nitems = N * 64;
-    const GradValueFixedArgs g{ref, off, logits, grad_out, grad_value, scratch, off_pitch, logit_pitch, H, W, Lq, PL, nitems,
-                               dfx::fixed::fraction_bits(dfx::fixed::msda_terms(Lq))};
-    static const int ncu = persistent_grid();
-    const int grid = nitems < ncu ? nitems : ncu;
-    const int S = H * W;
-    // algorithmic bytes: every quad of a head reads the head's offsets, logits and reference points again
-    const long bytes = 4L * ((long)N * Lq * (256 + 64 + 32 + ref_dim) + (long)N * S * 256);
-    if (ref_dim == 2) dfx::launch_timed(bytes, Lq, S, msda_level_grad_value_fixed<2>, dim3((unsigned)grid), dim3(THREADS), lds, st, g);
-    else dfx::launch_timed(bytes, Lq, S, msda_level_grad_value_fixed<4>, dim3((unsigned)grid), dim3(THREADS), lds, st, g);
-    return dfx::check_launch("msda_level_grad_value_fixed");
+    return launch_grad_value<FixedSum>("msda level grad_value (fixed)", "msda_level_grad_value_fixed", ref, ref_dim, off, off_pitch,
+                                       logits, logit_pitch, grad_out, N, H, W, Lq, grad_value, scratch, stream);
 }
 
 extern "C" int dfx_msda_level_grad_value_f32(const float *ref, int ref_dim, const float *off, long off_pitch,
                                              const float *logits, long logit_pitch, const float *grad_out, int N, int H,
                                              int W, int Lq, float *grad_value, void *stream)
 {
-    const char *what = "msda level grad_value";
-    if (N < 0 || H <= 0 || W <= 0 || Lq < 0) return dfx::fail(DFX_EINVAL, "%s: bad dimension", what);
-    if (N == 0) return DFX_OK;
-    if (const int rc = check_level_args(what, ref, ref_dim, off, off_pitch, logits, logit_pitch, grad_out, N, H, W, Lq, grad_value))
-        return rc;
-    const int PL = (int)plane_tokens(H, W);
-    const size_t lds = (size_t)2 * PL * 16;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (const int rc = dfx::raise_lds_limit<&msda_level_grad_value<2>, &msda_level_grad_value<4>>("msda level grad_value",
-                                                                                                 (int)LDS_CAP))
-        return rc;
-    const int nitems = N * 32;
-    const GradValueArgs g{ref, off, logits, grad_out, grad_value, off_pitch, logit_pitch, H, W, Lq, PL, nitems};
-    // persistent: at most one workgroup per CU, a multiple of 8 so that item & 7 (the head) is fixed per workgroup; the CU
-    // count is that of the device of the first call (as the forward's grid), the machines this runs on being uniform
-    static const int ncu = persistent_grid();
-    const int grid = nitems < ncu ? nitems : ncu;
-    const int S = H * W;
-    // algorithmic bytes of this launch: grad_out + offsets + logits + reference points read, grad_value written
-    const long bytes = 4L * ((long)N * Lq * (256 + 64 + 32 + ref_dim) + (long)N * S * 256);
-    if (ref_dim == 2) dfx::launch_timed(bytes, Lq, S, msda_level_grad_value<2>, dim3((unsigned)grid), dim3(THREADS), lds, st, g);
-    else dfx::launch_timed(bytes, Lq, S, msda_level_grad_value<4>, dim3((unsigned)grid), dim3(THREADS), lds, st, g);
-    return dfx::check_launch("msda_level_grad_value");
+    return launch_grad_value<FloatSum>("msda level grad_value", "msda_level_grad_value", ref, ref_dim, off, off_pitch, logits,
+                                       logit_pitch, grad_out, N, H, W, Lq, grad_value, nullptr, stream);
 }

@@ -1,5 +1,6 @@
-"""Shared builders of the inference kernel tests (csrc/fused_epilogue.hip, csrc/groupnorm.hip, the forward of
-csrc/dynconv.hip): seeded fp64 CPU inputs of fp32-representable values and a plain restatement of each operator in the
+"""Shared builders of the inference kernel tests (csrc/fused_epilogue.hip, add_layernorm of csrc/layernorm_train.hip,
+csrc/groupnorm.hip, the forward of csrc/dynconv.hip): seeded fp64 CPU inputs of fp32-representable values and a plain
+restatement of each operator in the
 dtype of its arguments.  The restatement is used twice: in fp64 it is the reference, in fp32 on the CPU it is the
 yardstick - the GPU tests allow ``YARDSTICK_FACTOR`` x its error, error relative to the reference's largest magnitude,
 the yardstick floored at one fp32 ulp (``yardstick``).

@@ -12,9 +12,13 @@ from tests import _msda_fused_cases as fc
 M, D, P = fc.M, fc.D, fc.P
 # (H, W, N, Lq, strided rows): fewer queries than the 1024 threads; a thread's second query; the 146 KB image of the
 # 50 x 84 level (the LDS opt-in); 288 items on 256 CUs (the persistent loop, re-zeroing between items); a 1 x 1 level;
-# offsets and logits as column slices of a wider buffer
+# offsets and logits as column slices of a wider buffer; a one-row and a one-column level with a single query (the flush
+# walk's carry: every step a new row at W = 1); 1032 tokens with 1025 queries (a third flush pass of the float policy's
+# 512 tokens per pass, a second of the fixed policy's 1024; one thread with a second query).  N = 9 is 288 float and
+# 576 fixed items.  No queries at all cannot stand here (a case needs samples to check its own construction): the
+# entry tests of both routes hold it (test_entry_writes_every_element_once_and_nothing_else, test_edges_give_exact_zeros).
 KERNEL_CASES = [(5, 7, 3, 37, False), (20, 31, 2, 1100, False), (50, 84, 1, 1100, False), (5, 7, 9, 37, False),
-                (1, 1, 2, 5, False), (5, 7, 3, 37, True)]
+                (1, 1, 2, 5, False), (5, 7, 3, 37, True), (1, 7, 2, 1, False), (7, 1, 2, 1, False), (24, 43, 1, 1025, False)]
 
 
 @functools.lru_cache(maxsize=None)

@@ -1,5 +1,6 @@
-"""GPU: the kernels every inference run goes through - bias_act, bias_relu_maxpool, add_layernorm, box_refine
-(csrc/fused_epilogue.hip), group_norm (csrc/groupnorm.hip) and the DynamicConv forward (csrc/dynconv.hip) - against the
+"""GPU: the kernels every inference run goes through - bias_act, bias_relu_maxpool, box_refine
+(csrc/fused_epilogue.hip), add_layernorm (csrc/layernorm_train.hip), group_norm (csrc/groupnorm.hip) and the
+DynamicConv forward (csrc/dynconv.hip) - against the
 fp64 restatements of tests/_inference_kernel_cases.py.  The rule is the project's: error relative to the reference's
 largest magnitude, at most 4 x the error of the same computation in fp32 on the CPU (floored at one fp32 ulp), printed
 per output and case; what is exact is asserted with torch.equal.  One case per launch regime and template

@@ -19,6 +19,7 @@ medians and every repetition's total (the spread is what a difference has to exc
 
     python tools/bench_addln_train.py [--iters 20] [--warmup 3] [--reps 3] [--pkg DIR] [--label NAME] [--no-layer]
     python tools/bench_addln_train.py --parent-pkg DIR [--rounds 2] [--out FILE]
+    python tools/bench_addln_train.py --inference [--iters 20] [--warmup 3] [--reps 3]       (ops.add_layernorm alone)
 """
 import argparse
 import json
@@ -129,6 +130,39 @@ def measure(args):
     return records
 
 
+def measure_inference(args):
+    """--inference: ops.add_layernorm alone (the inference tail, no autograd) at C = 256, 32 x 4200 and 32 x 300 rows, with and
+    without a residual: HIP events around --iters x 10 launches, the median of --reps repetitions in microseconds per launch."""
+    sys.path.insert(0, os.path.abspath(args.pkg))
+    import torch
+    from torch import nn
+    from dfx import ops
+    assert torch.cuda.is_available(), "this tool measures on the GPU"
+    norm = nn.LayerNorm(C).cuda().eval()
+    records = []
+    with torch.no_grad():
+        for frames, tokens in ((32, 4200), (32, 300)):
+            g = torch.Generator().manual_seed(frames * tokens)
+            x, r = (torch.randn(frames, tokens, C, generator=g).cuda() for _ in range(2))
+            for res in (r, None):
+                what = f"add_layernorm {frames} x {tokens} {'residual' if res is not None else 'no residual'}"
+                for _ in range(args.warmup):
+                    ops.add_layernorm(x, res, norm)
+                reps = []
+                for _ in range(args.reps):
+                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    a.record()
+                    for _ in range(args.iters * 10):
+                        ops.add_layernorm(x, res, norm)
+                    b.record()
+                    torch.cuda.synchronize()
+                    reps.append(a.elapsed_time(b) * 1e3 / (args.iters * 10))
+                records.append({"label": args.label, "what": what, "us": statistics.median(reps), "reps_us": reps})
+                print(f"[{args.label}] [{what:40s}] median {records[-1]['us']:8.2f} us  reps {' '.join(f'{t:.2f}' for t in reps)}", flush=True)
+    print("RESULT " + json.dumps(records), flush=True)
+    return records
+
+
 def compare(args):
     """Alternates child processes on this tree and on the parent's package; medians over the rounds, one table."""
     runs = {}
@@ -177,8 +211,11 @@ def main():
     ap.add_argument("--no-layer", action="store_true")
     ap.add_argument("--child-timeout", type=float, default=300.0)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--inference", action="store_true", help="time ops.add_layernorm (no autograd) instead of the training tails")
     args = ap.parse_args()
-    if args.parent_pkg:
+    if args.inference:
+        measure_inference(args)
+    elif args.parent_pkg:
         compare(args)
     else:
         measure(args)

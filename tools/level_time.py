@@ -1,5 +1,7 @@
 """Stamped duration of the level-in-LDS MSDA kernel (block-major operands, encoder geometry 50 x 84) for N frames with
-per-query offsets of `spread` px:  python tools/level_time.py [spread]   (DFX_LEVEL_NOT_PERSISTENT=1: one workgroup per item)"""
+per-query offsets of `spread` px:  python tools/level_time.py [spread]   (DFX_LEVEL_NOT_PERSISTENT=1: one workgroup per item)
+python tools/level_time.py --backward: the same stamps for the grad_value kernel of the level's backward (csrc/msda_level_backward.hip),
+float and fixed-point policy, 4 and 32 frames of 4200 and of 300 queries; median and smallest of 40 launches each."""
 import os
 import sys
 
@@ -8,11 +10,35 @@ import torch
 
 from dfx import ops
 
-spread = float(sys.argv[1]) if len(sys.argv) > 1 else 2.5
 dev = torch.device("cuda:0")
 H, W = 50, 84
 S = H * W
 torch.manual_seed(0)
+
+
+def backward():
+    for N, Lq in ((4, 4200), (32, 4200), (4, 300), (32, 300)):
+        g = torch.Generator().manual_seed(N + Lq)
+        grad_out, logits = torch.randn(N, Lq, 256, generator=g).to(dev), torch.randn(N, Lq, 32, generator=g).to(dev)
+        offsets = (2.5 * torch.randn(N, Lq, 64, generator=g)).to(dev)
+        ref = torch.rand(N, Lq, 1, 2, generator=g).to(dev)
+        for fixed in (False, True):
+            for _ in range(3):
+                ops.msda_level_grad_value(grad_out, ref, offsets, logits, N, H, W, deterministic=fixed)
+            torch.cuda.synchronize()
+            ops.profile_start()
+            for _ in range(40):
+                ops.msda_level_grad_value(grad_out, ref, offsets, logits, N, H, W, deterministic=fixed)
+            torch.cuda.synchronize()
+            t = sorted(r[0] for r in ops.profile_stop() if (r[2], r[3]) == (Lq, S))
+            assert len(t) == 40, len(t)
+            print(f"[level] [grad_value {'fixed' if fixed else 'float'} {N:2d} x {Lq:4d}] median {t[20] * 1e6:8.2f} us  min {t[0] * 1e6:8.2f} us", flush=True)
+
+
+if "--backward" in sys.argv[1:]:
+    backward()
+    sys.exit(0)
+spread = float(sys.argv[1]) if len(sys.argv) > 1 else 2.5
 for N in (32, 8, 4):
     value_blk = torch.randn(64, N * S, 4, device=dev)
     qproj = torch.randn(8, N * S, 12, device=dev)
