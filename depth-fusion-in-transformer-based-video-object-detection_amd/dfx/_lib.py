@@ -92,7 +92,17 @@ SIGNATURES = {
     "dfx_conv2d_tile_f32": [_p, _p, _p, _p] + [_i] * 13 + [_l, _p],
     "dfx_conv3x3_wino_f32": [_p, _p, _p, _p] + [_i] * 7 + [_p],
     "dfx_wino_weights_f32": [_p, _p, _p, _i, _i, _p],
+    # include/dfx_criterion.h: logits, boxes, tgt_labels, tgt_boxes, desc, S, B, rows, Ttot, cost weights x 3, cost, stream
+    "dfx_match_cost_f32": [_p] * 5 + [_i] * 4 + [ctypes.c_float] * 3 + [_p, _p],
+    # logits, boxes, tgt_labels, tgt_boxes, row_target, desc, S, B, rows, Ttot, 1/num_boxes, out, stream
+    "dfx_set_loss_forward_f32": [_p] * 6 + [_i] * 4 + [ctypes.c_double, _p, _p],
+    # grad_out, the forward's six pointers, S, B, rows, Ttot, 1/num_boxes, grad_logits | NULL, grad_boxes | NULL, stream
+    "dfx_set_loss_backward_f32": [_p] * 7 + [_i] * 4 + [ctypes.c_double, _p, _p, _p],
+    # host code, host pointers: cost [Q,T], Q, T, rows, cols;  cost, desc, S, B, rows, Ttot, row_target
+    "dfx_lsap_f32": [_p, _i, _i, _p, _p],
+    "dfx_lsap_ragged_f32": [_p, _p, _i, _i, _i, _i, _p],
 }
+ENONFINITE = -4       # DFX_ENONFINITE of include/dfx_criterion.h
 
 
 class LevelLayout(ctypes.Structure):

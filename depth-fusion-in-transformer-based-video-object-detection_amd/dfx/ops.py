@@ -1670,3 +1670,129 @@ def batch_norm_train(x, bn, act=None):
     if track and bn.num_batches_tracked is not None:
         bn.num_batches_tracked.add_(1)
     return y
+
+
+# ---- training criterion (include/dfx_criterion.h, csrc/criterion.hip) ------------------------------------------------
+def criterion_layout(queries, zero_labels, counts):
+    """The ragged layout of one criterion call -> (descriptor as a list of ints, (S, B, rows, Ttot)).  ``queries``: Q_s per
+    prediction set, ``zero_labels``: per set, "its labels are all 0" (enc_outputs), ``counts``: targets per image."""
+    S, B = len(queries), len(counts)
+    desc, row = [], 0
+    for Q, zero in zip(queries, zero_labels):
+        desc += [int(Q), row, int(bool(zero))]
+        row += B * int(Q)
+    off = [0]
+    for n in counts:
+        off.append(off[-1] + int(n))
+    _require(row * 4 < 2 ** 31 and sum(queries) * off[-1] < 2 ** 31, "criterion_layout: too many rows or pairs")
+    return desc + off, (S, B, row, off[-1])
+
+
+def _criterion_operands(what, logits, boxes, tgt_labels, tgt_boxes, desc, dims):
+    S, B, rows, Ttot = dims
+    _check_inputs([("logits", logits), ("boxes", boxes), ("tgt_labels", tgt_labels), ("tgt_boxes", tgt_boxes), ("desc", desc)])
+    _require(logits.dtype == torch.float32 and boxes.dtype == torch.float32 and tgt_boxes.dtype == torch.float32
+             and tgt_labels.dtype == torch.int32 and desc.dtype == torch.int32, f"{what}: fp32 operands, int32 labels and descriptor")
+    _require(tuple(logits.shape) == (rows, 3) and tuple(boxes.shape) == (rows, 4) and tgt_labels.numel() == Ttot
+             and tgt_boxes.numel() == 4 * Ttot and desc.numel() == 3 * S + B + 1,
+             f"{what}: logits [rows,3] (the reference's three-column loss), boxes [rows,4], labels [Ttot], target boxes [Ttot,4], "
+             "descriptor 3*S + B + 1 ints")
+
+
+def match_cost(logits, boxes, tgt_labels, tgt_boxes, desc, dims, cost_class, cost_bbox, cost_giou):
+    """Matching costs of every (set, image, query, target of that image) pair in one launch -> flat fp32 [sum(Q) * Ttot]:
+    block (s, b) is a row-major [Q_s, T_b] matrix at Ttot * sum(Q_s' < s) + Q_s * tgt_off[b] (dfx_match_cost_f32)."""
+    _criterion_operands("match_cost", logits, boxes, tgt_labels, tgt_boxes, desc, dims)
+    S, B, rows, Ttot = dims
+    cost = torch.empty(((rows // B if B else 0) * Ttot,), dtype=torch.float32, device=logits.device)
+    _call("match_cost", "dfx_match_cost_f32", logits.device, logits.data_ptr(), boxes.data_ptr(), tgt_labels.data_ptr(),
+          tgt_boxes.data_ptr(), desc.data_ptr(), S, B, rows, Ttot, float(cost_class), float(cost_bbox), float(cost_giou), cost.data_ptr())
+    return cost
+
+
+def _lsap_check(rc, what):
+    if rc == _lib.ENONFINITE:
+        raise ValueError("matrix contains invalid numeric entries")          # scipy's wording for the same input
+    if rc != 0:
+        _lib.check(rc, what)
+
+
+def lsap(cost):
+    """Rectangular linear sum assignment of a [Q, T] matrix in host memory (dfx_lsap_f32: host code, shortest augmenting
+    paths, double accumulation over the fp32 entries) -> (rows, cols): min(Q, T) int64 indices each, sorted by row.  A NaN
+    or infinite entry raises ValueError, as scipy.optimize.linear_sum_assignment does."""
+    cost = torch.as_tensor(cost)
+    _require(cost.dim() == 2 and not cost.is_cuda, "lsap: a 2-d matrix in host memory")
+    cost = cost.to(torch.float32).contiguous()
+    Q, T = cost.shape
+    n = min(Q, T)
+    rows, cols = torch.empty(n, dtype=torch.int32), torch.empty(n, dtype=torch.int32)
+    _lsap_check(_lib.load().dfx_lsap_f32(cost.data_ptr(), Q, T, rows.data_ptr(), cols.data_ptr()), "lsap")
+    return rows.long(), cols.long()
+
+
+def lsap_ragged(cost, desc, dims, row_target=None):
+    """dfx_lsap_f32 on every block of a ``match_cost`` result held in HOST memory (fp32, flat), ``desc`` the descriptor in host
+    memory (int32) -> row_target [rows] int32 in host memory (``row_target`` when given): global target index or -1."""
+    S, B, rows, Ttot = dims
+    _require(not cost.is_cuda and not desc.is_cuda and cost.dtype == torch.float32 and desc.dtype == torch.int32
+             and cost.is_contiguous() and desc.is_contiguous() and cost.numel() >= (rows // B if B else 0) * Ttot
+             and desc.numel() >= 3 * S + B + 1, "lsap_ragged: contiguous fp32 costs and int32 descriptor in host memory")
+    if row_target is None:
+        row_target = torch.empty(rows, dtype=torch.int32)
+    _require(not row_target.is_cuda and row_target.dtype == torch.int32 and row_target.is_contiguous()
+             and row_target.numel() >= rows, "lsap_ragged: row_target is int32 [rows] in host memory")
+    _lsap_check(_lib.load().dfx_lsap_ragged_f32(cost.data_ptr(), desc.data_ptr(), S, B, rows, Ttot, row_target.data_ptr()), "lsap_ragged")
+    return row_target
+
+
+def set_loss_forward(logits, boxes, tgt_labels, tgt_boxes, row_target, desc, dims, inv_num_boxes):
+    """-> out [S, 5] fp32 = loss_ce, class_error, loss_bbox, loss_giou, cardinality_error of every set, one launch
+    (dfx_set_loss_forward_f32); ``row_target`` [rows] int32 on the device."""
+    _criterion_operands("set_loss_forward", logits, boxes, tgt_labels, tgt_boxes, desc, dims)
+    S, B, rows, Ttot = dims
+    _check_inputs([("logits", logits), ("row_target", row_target)])
+    _require(row_target.dtype == torch.int32 and row_target.numel() == rows, "set_loss_forward: row_target is int32 [rows]")
+    out = torch.empty((S, 5), dtype=torch.float32, device=logits.device)
+    _call("set_loss_forward", "dfx_set_loss_forward_f32", logits.device, logits.data_ptr(), boxes.data_ptr(), tgt_labels.data_ptr(),
+          tgt_boxes.data_ptr(), row_target.data_ptr(), desc.data_ptr(), S, B, rows, Ttot, float(inv_num_boxes), out.data_ptr())
+    return out
+
+
+def set_loss_backward(grad_out, logits, boxes, tgt_labels, tgt_boxes, row_target, desc, dims, inv_num_boxes,
+                      need_logits=True, need_boxes=True):
+    """Gradients of sum(grad_out * out) of ``set_loss_forward`` in closed form, one launch -> (grad_logits | None,
+    grad_boxes | None), fresh tensors written in full (dfx_set_loss_backward_f32).  Column 0 of grad_logits and the box
+    gradient of unmatched rows are exact zeros."""
+    _criterion_operands("set_loss_backward", logits, boxes, tgt_labels, tgt_boxes, desc, dims)
+    S, B, rows, Ttot = dims
+    _check_inputs([("logits", logits), ("row_target", row_target), ("grad_out", grad_out)])
+    _require(row_target.dtype == torch.int32 and row_target.numel() == rows and grad_out.dtype == torch.float32
+             and tuple(grad_out.shape) == (S, 5), "set_loss_backward: row_target is int32 [rows], grad_out fp32 [S,5]")
+    grad_logits = torch.empty_like(logits) if need_logits else None
+    grad_boxes = torch.empty_like(boxes) if need_boxes else None
+    if need_logits or need_boxes:
+        _call("set_loss_backward", "dfx_set_loss_backward_f32", logits.device, grad_out.data_ptr(), logits.data_ptr(), boxes.data_ptr(),
+              tgt_labels.data_ptr(), tgt_boxes.data_ptr(), row_target.data_ptr(), desc.data_ptr(), S, B, rows, Ttot,
+              float(inv_num_boxes), _ptr(grad_logits), _ptr(grad_boxes))
+    return grad_logits, grad_boxes
+
+
+class SetLossFunction(torch.autograd.Function):
+    """apply(logits [rows,3], boxes [rows,4], tgt_labels, tgt_boxes, row_target, desc, dims, inv_num_boxes) -> out [S,5].
+    Keeps its inputs, row_target and the descriptor - nothing of the forward's arithmetic; columns 1 and 4 of the result
+    (class_error, cardinality_error) have no gradient."""
+
+    @staticmethod
+    def forward(ctx, logits, boxes, tgt_labels, tgt_boxes, row_target, desc, dims, inv_num_boxes):
+        out = set_loss_forward(logits, boxes, tgt_labels, tgt_boxes, row_target, desc, dims, inv_num_boxes)
+        ctx.save_for_backward(logits, boxes, tgt_labels, tgt_boxes, row_target, desc)
+        ctx.dims, ctx.inv_num_boxes = dims, inv_num_boxes
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        need = ctx.needs_input_grad
+        gl, gb = set_loss_backward(grad_out.contiguous(), *ctx.saved_tensors, ctx.dims, ctx.inv_num_boxes,
+                                   need_logits=need[0], need_boxes=need[1])
+        return gl, gb, None, None, None, None, None, None

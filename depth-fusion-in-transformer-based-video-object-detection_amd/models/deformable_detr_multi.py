@@ -12,6 +12,8 @@ from util.misc_multi import NestedTensor, nested_tensor_from_tensor_list
 from .deformable_transformer_multi import build_deforamble_transformer
 from .detector_common import (MLP, DetectorBase, PostProcess, TrainingOnly, _prior_bias, _zero_last_layer,  # noqa: F401
                               apply_box_head, build_backbones, loss_weight_dict)
+from .criterion import SetCriterion  # noqa: F401
+from .matcher import build_matcher
 
 
 class DeformableDETR(DetectorBase):
@@ -58,5 +60,6 @@ def build(args):
                            num_ref_frames=args.num_ref_frames, aux_loss=args.aux_loss,
                            with_box_refine=args.with_box_refine, two_stage=args.two_stage,
                            use_depth=args.use_depth, depth_type=args.depth_type)
-    criterion = TrainingOnly(loss_weight_dict(args))
+    criterion = SetCriterion(args.num_classes, build_matcher(args), loss_weight_dict(args), ["labels", "boxes", "cardinality"],
+                             focal_alpha=args.focal_alpha)
     return model, criterion, {"bbox": PostProcess()}

@@ -16,6 +16,8 @@ from util.misc_multi import NestedTensor, inverse_sigmoid, nested_tensor_from_te
 from .deformable_transformer_multi_plusplus import build_deforamble_transformer
 from .detector_common import (MLP, DetectorBase, PostProcess, TrainingOnly, _prior_bias, _zero_last_layer,  # noqa: F401
                               apply_box_head, build_backbones, loss_weight_dict)
+from .criterion import SetCriterion  # noqa: F401
+from .matcher import build_matcher
 
 
 class DeformableDETR(DetectorBase):
@@ -73,5 +75,6 @@ def build(args):
                            num_ref_frames=args.num_ref_frames, aux_loss=args.aux_loss,
                            with_box_refine=args.with_box_refine, two_stage=args.two_stage,
                            use_depth=args.use_depth, depth_type=args.depth_type)
-    criterion = TrainingOnly(loss_weight_dict(args))
+    criterion = SetCriterion(args.num_classes, build_matcher(args), loss_weight_dict(args), ["labels", "boxes", "cardinality"],
+                             focal_alpha=args.focal_alpha)
     return model, criterion, {"bbox": PostProcess()}

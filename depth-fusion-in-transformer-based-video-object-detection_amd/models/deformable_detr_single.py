@@ -9,6 +9,8 @@ from util.misc import NestedTensor, inverse_sigmoid, nested_tensor_from_tensor_l
 from .deformable_transformer_single import build_deforamble_transformer
 from .detector_common import (MLP, DetectorBase, PostProcess, TrainingOnly, apply_box_head,  # noqa: F401
                               build_backbones, loss_weight_dict)
+from .criterion import SetCriterion  # noqa: F401
+from .matcher import build_matcher
 
 
 class DeformableDETR(DetectorBase):
@@ -53,5 +55,6 @@ def build(args):
                            num_queries=args.num_queries, num_feature_levels=args.num_feature_levels,
                            aux_loss=args.aux_loss, with_box_refine=args.with_box_refine, two_stage=args.two_stage,
                            use_depth=args.use_depth, depth_type=args.depth_type)
-    criterion = TrainingOnly(loss_weight_dict(args))
+    criterion = SetCriterion(args.num_classes, build_matcher(args), loss_weight_dict(args), ["labels", "boxes", "cardinality"],
+                             focal_alpha=args.focal_alpha)
     return model, criterion, {"bbox": PostProcess()}
