@@ -101,6 +101,11 @@ SIGNATURES = {
     # host code, host pointers: cost [Q,T], Q, T, rows, cols;  cost, desc, S, B, rows, Ttot, row_target
     "dfx_lsap_f32": [_p, _i, _i, _p, _p],
     "dfx_lsap_ragged_f32": [_p, _p, _i, _i, _i, _i, _p],
+    # include/dfx_optim.h: tensors, chunks, n_chunks, partials, stream
+    "dfx_optim_chunk_elements": [],
+    "dfx_grad_sqnorm_f32": [_p, _p, _i, _p, _p],
+    # tensors, chunks, n_chunks, partials | NULL, max_norm, norm_out | NULL, stream
+    "dfx_adamw_step_f32": [_p, _p, _i, _p, ctypes.c_float, _p, _p],
 }
 ENONFINITE = -4       # DFX_ENONFINITE of include/dfx_criterion.h
 
