@@ -354,5 +354,123 @@ __device__ __forceinline__ void epilogue_scalar(const f32x16 (&acc)[T::MT][T::NT
     }
 }
 
+// ---- bf16 operands (gemm_bf16.hip) -------------------------------------------------------------------------------------------
+// v_mfma_f32_32x32x16_bf16: the accumulator layout is the fp32 MFMA's (acc_row, acc_to_lds and the tile geometry above apply as
+// they are); lane (c, half) holds A[row c][k = 8 half + j] and B[k = 8 half + j][col c], j = 0 .. 7, of a 16-deep step.
+using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
+
+// two fp32 -> one dword of two bf16 (lo in bits 0 .. 15), round-to-nearest-even: what tensor.to(torch.bfloat16) does
+__device__ __forceinline__ unsigned pack_bf16(float lo, float hi)
+{
+    unsigned r;
+    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
+    return r;
+}
+__device__ __forceinline__ u32x4 pack_bf16x8(const f32x4 &a, const f32x4 &b)
+{
+    return (u32x4){pack_bf16(a[0], a[1]), pack_bf16(a[2], a[3]), pack_bf16(b[0], b[1]), pack_bf16(b[2], b[3])};
+}
+
+// One stage holds BK k of the tile in bf16, both operands K-contiguous: As[m][k], Bs[n][k] with a row pitch of BK + 8 elements
+// (BK = 32: five 16-byte slots, so the 16 lanes of a ds_read_b128 group - 16 rows, the same k - fall on 16 different slots).
+// A ds_read_b128 at [row][16 s + 8 half] is the lane's operand of the s-th 16-deep MFMA of the step.
+template <class T, int BK>
+__device__ __forceinline__ void kstep_bf16(const unsigned short *As, const unsigned short *Bs, const Lane &l, f32x16 (&acc)[T::MT][T::NT])
+{
+    constexpr int LD = BK + 8;
+    bf16x8 af[BK / 16][T::MT], bf[BK / 16][T::NT];
+#pragma unroll
+    for (int s = 0; s < BK / 16; ++s) {
+#pragma unroll
+        for (int i = 0; i < T::MT; ++i) af[s][i] = *reinterpret_cast<const bf16x8 *>(&As[(l.wm * T::TM + i * 32 + l.c) * LD + s * 16 + l.half * 8]);
+#pragma unroll
+        for (int j = 0; j < T::NT; ++j) bf[s][j] = *reinterpret_cast<const bf16x8 *>(&Bs[(l.wn * T::TN + j * 32 + l.c) * LD + s * 16 + l.half * 8]);
+    }
+#pragma unroll
+    for (int s = 0; s < BK / 16; ++s)
+#pragma unroll
+        for (int i = 0; i < T::MT; ++i)
+#pragma unroll
+            for (int j = 0; j < T::NT; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[s][i], bf[s][j], acc[i][j], 0, 0, 0);
+}
+
+// C[m][n] = act(acc + bias[n] + R[m][n]) in fp32, stored as fp32 or - rounded once - as bf16
+struct EpilogueOut {
+    void *C = nullptr;
+    long ldc = 0;
+    const float *R = nullptr;
+    long ldr = 0;
+    const float *bias = nullptr;
+    int M = 0, N = 0, act = 0;
+};
+
+// The 8-column form (N % 8 == 0, rows of C - and of R - 16-byte aligned): the tile goes through LDS as in the float4 forms, a
+// thread keeps one column octet (its bias loaded once) and a row leaves as two float4 or as one 16-byte store of 8 bf16.
+template <class T, bool C_BF16>
+__device__ __forceinline__ void epilogue_oct(float *Ct, const f32x16 (&acc)[T::MT][T::NT], const Lane &l, int m0, int n0, const EpilogueOut &e)
+{
+    constexpr int OQ = T::BN / 8, RS = T::NTHR / OQ, NIT = T::PR / RS;
+    static_assert(T::NTHR % OQ == 0 && T::PR % RS == 0, "a pass is a whole number of thread rows");
+    const int o = l.tid % OQ, r0 = l.tid / OQ, n = n0 + o * 8;
+    const bool ncol = n < e.N;                      // (N % 8 == 0: an octet lies inside or outside)
+    f32x4 b0 = {0.f, 0.f, 0.f, 0.f}, b1 = b0;
+    if (e.bias && ncol) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) b0[u] = e.bias[n + u], b1[u] = e.bias[n + 4 + u];
+    }
+#pragma unroll
+    for (int p = 0; p < T::BM / T::PR; ++p) {
+        if (p > 0) __syncthreads();
+        acc_to_lds<T>(Ct, acc, l, p);
+        __syncthreads();
+#pragma unroll
+        for (int it = 0; it < NIT; ++it) {
+            const int row = r0 + it * RS, m = m0 + T::tile_row(p, row);
+            if (m >= e.M || !ncol) continue;
+            f32x4 v0 = *reinterpret_cast<const f32x4 *>(&Ct[row * T::LDC + o * 8]) + b0;
+            f32x4 v1 = *reinterpret_cast<const f32x4 *>(&Ct[row * T::LDC + o * 8 + 4]) + b1;
+            if (e.R) {
+                const f32x4 *r = reinterpret_cast<const f32x4 *>(e.R + (long)m * e.ldr + n);
+                v0 += r[0], v1 += r[1];
+            }
+            if (e.act) {
+#pragma unroll
+                for (int u = 0; u < 4; ++u) v0[u] = activate(v0[u], e.act), v1[u] = activate(v1[u], e.act);
+            }
+            if (C_BF16) {
+                *reinterpret_cast<u32x4 *>(static_cast<unsigned short *>(e.C) + (long)m * e.ldc + n) = pack_bf16x8(v0, v1);
+            } else {
+                f32x4 *c = reinterpret_cast<f32x4 *>(static_cast<float *>(e.C) + (long)m * e.ldc + n);
+                c[0] = v0, c[1] = v1;
+            }
+        }
+    }
+}
+
+// The scalar form, straight from the accumulators: any N, rows of C aligned to one element only
+template <class T, bool C_BF16>
+__device__ __forceinline__ void epilogue_scalar_out(const f32x16 (&acc)[T::MT][T::NT], const Lane &l, int m0, int n0, const EpilogueOut &e)
+{
+#pragma unroll
+    for (int j = 0; j < T::NT; ++j) {
+        const int n = n0 + l.wn * T::TN + j * 32 + l.c;
+        if (n >= e.N) continue;
+        const float b = e.bias ? e.bias[n] : 0.f;
+#pragma unroll
+        for (int i = 0; i < T::MT; ++i) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int m = m0 + l.wm * T::TM + i * 32 + acc_row(r, l.half);
+                if (m >= e.M) continue;
+                float v = acc[i][j][r] + b;
+                if (e.R) v += e.R[(long)m * e.ldr + n];
+                if (e.act) v = activate(v, e.act);
+                if (C_BF16) static_cast<unsigned short *>(e.C)[(long)m * e.ldc + n] = (unsigned short)(pack_bf16(v, v) & 0xffffu);
+                else static_cast<float *>(e.C)[(long)m * e.ldc + n] = v;
+            }
+        }
+    }
+}
+
 }  // namespace mfma
 }  // namespace dfx

@@ -67,6 +67,8 @@ SIGNATURES = {
     "dfx_gemm_wgrad_f32": [_p, _l, _p, _l, _p, _l, _p, _i, _i, _i, _i, _p, _p],
     # dZ, image stride, X, image stride, dW, Co, Ci, HW, batch, splits, workspace | NULL, stream (csrc/gemm_f32.hip)
     "dfx_conv1x1_wgrad_f32": [_p, _l, _p, _l, _p, _i, _i, _i, _i, _i, _p, _p],
+    # include/dfx_gemm_bf16.h: A, a_dtype, lda, W (bf16), ldw, bias | NULL, R | NULL, ldr, C, c_dtype, ldc, M, N, K, act, stream
+    "dfx_gemm_bf16": [_p, _i, _l, _p, _l, _p, _p, _l, _p, _i, _l, _i, _i, _i, _i, _p],
     # include/dfx_fused.h: x, bias, residual, out, N, C, HW, relu, stream
     "dfx_bias_act_nchw_f32": [_p, _p, _p, _p, _i, _i, _l, _i, _p],
     "dfx_bias_relu_maxpool_f32": [_p, _p, _p, _i, _i, _i, _i, _p],

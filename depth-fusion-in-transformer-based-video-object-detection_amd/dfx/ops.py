@@ -768,6 +768,46 @@ def linear(x, weight, bias=None, relu=False, residual=None, add=None, row_mask=N
     return out
 
 
+_BF16_DTYPE_CODE = {torch.float32: 0, torch.bfloat16: 1}      # DFX_DT_* of include/dfx_gemm_bf16.h
+
+
+def linear_bf16(x, weight_bf16, bias=None, act=None, residual=None, out_dtype=torch.float32):
+    """y = act(x @ weight_bf16.T + bias (+ residual)) on the bf16 MFMA GEMM (include/dfx_gemm_bf16.h, csrc/gemm_bf16.hip):
+    bf16 products, fp32 accumulation, bias / residual / activation in fp32.
+    x [..., K] contiguous, fp32 (rounded to bf16 as ``x.to(torch.bfloat16)`` does, inside the kernel) or bf16; weight_bf16 [N, K]
+    bf16; bias [N] and residual [..., N] fp32.  act: None / "relu" / "gelu".  -> [..., N] in ``out_dtype`` (fp32, or bf16 rounded
+    once from the fp32 result).  K must be a multiple of 8."""
+    K = x.shape[-1]
+    N = weight_bf16.shape[0]
+    x2 = x.reshape(-1, K)
+    M = x2.shape[0]
+    named = [("x", x2), ("weight", weight_bf16)]
+    for nm, t in (("bias", bias), ("residual", residual)):
+        if t is not None:
+            named.append((nm, t))
+    # (dtypes and shapes first: they are refused the same way wherever the tensors live)
+    _require(x2.dtype in _BF16_DTYPE_CODE and out_dtype in _BF16_DTYPE_CODE, "linear_bf16: x and out_dtype must be float32 or bfloat16")
+    _require(weight_bf16.dtype == torch.bfloat16, "linear_bf16: the weight must be bfloat16")
+    _require(weight_bf16.dim() == 2 and weight_bf16.shape[1] == K and K % 8 == 0 and K > 0,
+             "linear_bf16: weight must be [N, K] with K a multiple of 8")
+    _check_inputs(named)
+    _require(bias is None or (bias.dtype == torch.float32 and bias.numel() == N), "linear_bf16: bias must be float32 [N]")
+    out = torch.empty(x.shape[:-1] + (N,), dtype=out_dtype, device=x.device)
+    if residual is not None:
+        _require(residual.dtype == torch.float32 and residual.shape == out.shape, "linear_bf16: residual must be float32 and match the output")
+    ea, ec = x2.element_size(), out.element_size()
+    # an operand of one call stays below 2 GiB (32-bit byte offsets): more rows go through in row ranges, as in linear()
+    rows_max = (_GEMM_MAX_BYTES - 1) // max(K * ea, N * ec, N * 4 if residual is not None else 1)
+    rows_max = max(128, rows_max // 128 * 128)
+    a_code, c_code, code = _BF16_DTYPE_CODE[x2.dtype], _BF16_DTYPE_CODE[out_dtype], ACT[act]
+    for r0 in range(0, M, rows_max):
+        r1 = min(M, r0 + rows_max)
+        _call("linear_bf16", "dfx_gemm_bf16", x.device, x2.data_ptr() + r0 * K * ea, a_code, K, weight_bf16.data_ptr(), K, _ptr(bias),
+              0 if residual is None else residual.data_ptr() + r0 * N * 4, N, out.data_ptr() + r0 * N * ec, c_code, N,
+              r1 - r0, N, K, code)
+    return out
+
+
 # ---- Linear in grad mode (include/dfx_gemm.h, dfx_gemm_wgrad_f32; csrc/gemm_wgrad.hip) ------------------------------------------
 # The split rule's two constants, both measured (tools/bench_linear_train.py, profiles/r14_linear_train.txt): ranges of at
 # least 16 row steps are 5-9 % ahead of 32-step ranges at 9600 rows (36 ranges against 18) and tie elsewhere; beyond ~256

@@ -67,6 +67,19 @@ DFORMER_TRAIN = os.environ.get("DFX_DFORMER_TRAIN", "1") != "0"
 DFORMER_TRAIN_MIN_PIXELS = 8 * 200 * 334
 DFORMER_TRAIN_MIN_PIXELS_GELU = 2 * 400 * 667
 
+# The FFNs of the transformer layers in GPU inference on the bf16 MFMA GEMM (dfx.ops.linear_bf16, csrc/gemm_bf16.hip): bf16 products,
+# fp32 accumulation, the 1024-wide hidden tensor kept in bf16, the residual add and the LayerNorm in fp32.  OFF by default: it
+# changes the results (every FFN input and weight is rounded to 8 significant bits; DESIGN.md 4k has the bounds and the
+# measured deviation).  DFX_LINEAR_BF16=1 turns it on.  Read once at import; the call sites (transformer_layers._ffn_bf16) read
+# this global at call time.  Taken where the fp32 fused FFN is taken today - fp32 GPU activations under no_grad, fp32 weights on
+# the same device, identity dropouts, a LayerNorm over 256 columns - when every in_features is a multiple of 8.  A
+# ClipRunner(graph=True) has captured the launches of one mode: call refresh() after toggling.
+LINEAR_BF16 = os.environ.get("DFX_LINEAR_BF16", "0") == "1"
+# No size rule: one FFN (two GEMMs + add_layernorm) MEASURED faster than the fp32 route beyond the repetition spread at every row
+# count tried - 1200 -> 413 us at 32 x 4200 rows (2.91x), 480 -> 139 us at 12 x 4200 (3.45x), 185 -> 57 us at 4 x 4200 (3.23x),
+# 112 -> 42.5 us at 9600 (2.64x), 50.2 -> 41.6 us at 300 (1.21x: host time there) - and so did the single-Linear GELU FFN of the
+# fusion layers (262 -> 157 us at 32 x 4200, 44 -> 28 us at 4 x 4200) (tools/bench_ffn_bf16.py, profiles/r21_ffn_bf16.txt).
+
 
 def derived_key(*sources):
     """The "have the sources changed" key of every tensor kept by an inference route that was DERIVED from weights (folded BN,
@@ -94,20 +107,48 @@ DERIVED_ATTRIBUTES = ("_folded", "_plans1x1", "_chain_carry", "_stem_folded",   
                       "_kv_stack")                                                               # models/fused_mha.py
 
 
+# ... and the one the opt-in bf16 FFN route keeps (bf16_weight below).  A tuple of its own: tests/test_weight_updates_cpu.py plants
+# exactly the names above and pins their number; drop_derived walks both.
+DERIVED_ATTRIBUTES_BF16 = ("_weight_bf16",)
+
+
 def drop_derived(model):
-    """Forget every tensor the fused inference routes of ``model`` derived from its weights: the DERIVED_ATTRIBUTES of every
-    submodule and the whole of ``util.memo``.  The next call rebuilds them, exactly as a module that has never run would.
+    """Forget every tensor the fused inference routes of ``model`` derived from its weights: the DERIVED_ATTRIBUTES (and
+    DERIVED_ATTRIBUTES_BF16) of every submodule and the whole of ``util.memo``.  The next call rebuilds them, exactly as a module
+    that has never run would.
     For edits no key can see (``derived_key``), and for whoever wants the memory back.  -> the number of entries dropped.
     (A ``ClipRunner(graph=True)`` keeps captured launches of its own: ``ClipRunner.refresh()``.)"""
     from util import memo
     n = 0
     for mod in model.modules():
-        for name in DERIVED_ATTRIBUTES:
+        for name in DERIVED_ATTRIBUTES + DERIVED_ATTRIBUTES_BF16:
             if mod.__dict__.pop(name, None) is not None:
                 n += 1
     n += len(memo._MEMO)
     memo.clear()
     return n
+
+
+def bf16_weight(linear):
+    """The bf16 copy of a Linear's weight for the LINEAR_BF16 route, [out_features, in_features] contiguous, rounded to nearest
+    even (``weight.to(torch.bfloat16)``).  Kept on the module (DERIVED_ATTRIBUTES_BF16) under ``derived_key(weight)`` plus the
+    device and rebuilt when that key changes; ``drop_derived`` forgets it."""
+    w = linear.weight
+    key = (derived_key(w), w.device)
+    kept = linear.__dict__.get("_weight_bf16")
+    if kept is None or kept[0] != key:
+        kept = (key, w.detach().to(torch.bfloat16).contiguous())
+        linear._weight_bf16 = kept
+    return kept[1]
+
+
+def linear_bf16_usable(x, *linears):
+    """May the FFN whose Linears are ``linears`` run on dfx.ops.linear_bf16 for the input ``x``?  Only as the LINEAR_BF16 comment
+    says.  (The switch is read here, at call time, from this module's globals.)"""
+    if not (LINEAR_BF16 and x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled() and x.numel() > 0):
+        return False
+    return all(l.in_features % 8 == 0 and l.weight.dtype == torch.float32 and l.weight.device == x.device
+               and (l.bias is None or (l.bias.dtype == torch.float32 and l.bias.device == x.device)) for l in linears)
 
 
 def needs_grad(part, *tensors):

@@ -96,6 +96,30 @@ def _linear_norm_add(linear, x, norm, residual=None, act=None, act_first=False, 
     return norm(y)
 
 
+def _ffn_bf16(x, linear1, activation, norm, linear2=None, mid_dropout=None, dropout=None):
+    """The FFN of a layer on the bf16 MFMA GEMM when models.fused.LINEAR_BF16 is on (off by default), else None:
+         norm(x + linear2(relu(linear1(x))))   hidden tensor in bf16, residual in linear2's epilogue, then add_layernorm
+         norm(x + gelu(linear1(x)))            (linear2 None: the fusion layers) fp32 out of the GEMM, then add_layernorm
+    in the situations that take the fp32 fused FFN (dfx.ops.linear(norm=...)): GPU inference, fp32 weights on x's device, a
+    LayerNorm over 256 columns, identity dropouts.  As many launches as the fp32 route."""
+    from models import fused
+    if not fused.LINEAR_BF16:
+        return None
+    last = linear1 if linear2 is None else linear2
+    if not (activation is (F.gelu if linear2 is None else F.relu) and last.out_features == 256 and norm.weight.is_cuda
+            and _identity_dropout(mid_dropout) and _identity_dropout(dropout)
+            and fused.linear_bf16_usable(x, *((linear1,) if linear2 is None else (linear1, linear2)))):
+        return None
+    from dfx import ops as _ops
+    x = x.contiguous()
+    if linear2 is None:
+        y = _ops.linear_bf16(x, fused.bf16_weight(linear1), linear1.bias, act="gelu")
+        return _ops.add_layernorm(y, x, norm)
+    h = _ops.linear_bf16(x, fused.bf16_weight(linear1), linear1.bias, act="relu", out_dtype=torch.bfloat16)
+    y = _ops.linear_bf16(h, fused.bf16_weight(linear2), linear2.bias, residual=x)
+    return _ops.add_layernorm(y, None, norm)
+
+
 def _norm_add(norm, x, y=None, dropout=None):
     """norm(x + dropout(y)).  Inference on the GPU: one fused pass (dfx.ops.add_layernorm); in grad mode with something to
     differentiate the fused forward / backward pair (dfx.ops.add_layernorm_train, models.fused.ADDLN_TRAIN); otherwise the
@@ -209,6 +233,9 @@ class DeformableTransformerEncoderLayer(nn.Module):
             y = self.self_attn(query, reference_points, src, spatial_shapes, level_start_index, padding_mask)
             src = _norm_add(self.norm1, src, y, dropout=self.dropout1)
         if fused and self.activation is F.relu:
+            y = _ffn_bf16(src, self.linear1, self.activation, self.norm2, self.linear2, self.dropout2, self.dropout3)
+            if y is not None:
+                return y
             from dfx import ops as _ops            # linear1 + bias + ReLU in one MFMA GEMM, linear2 + residual + LayerNorm in another
             h = _ops.linear(src.contiguous(), self.linear1.weight, self.linear1.bias, relu=True)
             return _linear_norm_add(self.linear2, self.dropout2(h), self.norm2, src, dropout=self.dropout3)
@@ -260,6 +287,9 @@ class _CrossFusionBlock(nn.Module):
 
     def forward_ffn(self, tgt):
         if (self.activation is F.gelu and tgt.is_cuda and tgt.dtype == torch.float32 and not torch.is_grad_enabled()):
+            y = _ffn_bf16(tgt, self.linear1, self.activation, getattr(self, self._ffn_norm), dropout=getattr(self, self._ffn_drop))
+            if y is not None:
+                return y
             from dfx import ops as _ops            # Linear + bias + exact GELU in one MFMA GEMM
             # ... then the residual add + LayerNorm in one launch behind it
             return _linear_norm_add(self.linear1, tgt, getattr(self, self._ffn_norm), tgt, act="gelu", act_first=True,
@@ -360,6 +390,9 @@ class DeformableTransformerDecoderLayer(nn.Module):
     with_pos_embed = staticmethod(_add_pos)
 
     def forward_ffn(self, tgt):
+        y = _ffn_bf16(tgt, self.linear1, self.activation, self.norm3, self.linear2, self.dropout3, self.dropout4)
+        if y is not None:
+            return y
         return _linear_norm_add(self.linear2, self.dropout3(_linear_act(self.linear1, self.activation, tgt)), self.norm3, tgt,
                                 dropout=self.dropout4)
 
@@ -464,6 +497,9 @@ class TemporalQueryEncoderLayer(nn.Module):
     with_pos_embed = staticmethod(_add_pos)
 
     def forward_ffn(self, tgt):
+        y = _ffn_bf16(tgt, self.linear1, self.activation, self.norm3, self.linear2, self.dropout3, self.dropout4)
+        if y is not None:
+            return y
         return _linear_norm_add(self.linear2, self.dropout3(_linear_act(self.linear1, self.activation, tgt)), self.norm3, tgt,
                                 dropout=self.dropout4)
 
@@ -525,6 +561,9 @@ class TemporalDeformableTransformerEncoderLayer(nn.Module):
     with_pos_embed = staticmethod(_add_pos)
 
     def forward_ffn(self, tgt):
+        y = _ffn_bf16(tgt, self.linear1, self.activation, self.norm3, self.linear2, self.dropout3, self.dropout4)
+        if y is not None:
+            return y
         return _linear_norm_add(self.linear2, self.dropout3(_linear_act(self.linear1, self.activation, tgt)), self.norm3, tgt,
                                 dropout=self.dropout4)
 
