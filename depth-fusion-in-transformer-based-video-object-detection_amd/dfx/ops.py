@@ -16,7 +16,8 @@ from . import _lib
 _SUFFIX = {torch.float32: "f32", torch.float64: "f64"}
 # 2-byte value maps (mixed precision, csrc/msda_forward.hip / msda_backward.hip): sampling_loc and attn_weight stay fp32
 _HALF_SUFFIX = {torch.bfloat16: "bf16", torch.float16: "f16"}
-ACT = {None: 0, "none": 0, "relu": 1, "gelu": 2}
+_C = _lib.CONSTANTS      # the headers' #defines: workspace sizes and codes are the library's, never restated here
+ACT = {None: _C["DFX_ACT_NONE"], "none": _C["DFX_ACT_NONE"], "relu": _C["DFX_ACT_RELU"], "gelu": _C["DFX_ACT_GELU"]}
 
 # Single-level attention with many queries (encoder, depth fusion) runs on the level-in-LDS kernel
 # (csrc/msda_level.hip) when the level fits the CU's LDS; DFX_MSDA_LEVEL=0 keeps the wave-per-query
@@ -687,6 +688,28 @@ def _split_k(M, N, K):
     return max(1, min(K // _SPLITK_RANGE, slots // tiles))
 
 
+def _gemm_f32(what, dev, A, B, C, M, N, K, lda, ldb, ldc, A2=0, strideA=0, strideB=0, b_is_kn=0, bias=0, bias_per_row=0,
+              R=0, ldr=0, strideR=0, row_mask=0, strideMask=0, strideC=0, batch=1, relu=0, c_block=0, c_block_stride=0,
+              a_block_stride=0):
+    """One ``dfx_gemm_f32`` launch under the parameter names of include/dfx_gemm.h, which documents them.  A, B, C and the
+    optional operands are device addresses; what a caller leaves out is absent (NULL, stride 0, a single batch)."""
+    _call(what, "dfx_gemm_f32", dev, A, A2, lda, strideA, B, ldb, strideB, b_is_kn, bias, bias_per_row, R, ldr, strideR,
+          row_mask, strideMask, C, ldc, strideC, M, N, K, batch, relu, c_block, c_block_stride, a_block_stride)
+
+
+def _row_ranges(M, row_bytes, rows_max=None):
+    """(r0, r1) row ranges that cover M rows.  The GEMM kernels address an operand with 32-bit byte offsets (buffer loads), so
+    one call's operands stay below ``_GEMM_MAX_BYTES`` (read here, at call time): at most that many rows of ``row_bytes``,
+    the widest operand's row - or ``rows_max`` where the caller has another cap - in whole multiples of 128, at least 128.
+    Every layout of these front ends is row-separable (strides are explicit arguments): a range is the same call on offset
+    pointers."""
+    if rows_max is None:
+        rows_max = (_GEMM_MAX_BYTES - 1) // row_bytes
+    rows_max = max(128, rows_max // 128 * 128)
+    for r0 in range(0, M, rows_max):
+        yield r0, min(M, r0 + rows_max)
+
+
 def linear(x, weight, bias=None, relu=False, residual=None, add=None, row_mask=None, col_block=0, x_blocked=False,
            act=None, norm=None, act_first=False):
     """y = act((x (+ add)) @ weight.T + bias (+ residual)), rows where row_mask is True set to 0.
@@ -749,26 +772,21 @@ def linear(x, weight, bias=None, relu=False, residual=None, add=None, row_mask=N
         _call("linear (split-K)", "dfx_gemm_splitk_f32", x.device, x2.data_ptr(), K, weight.data_ptr(), K, 0, _ptr(bias), 0,
               _ptr(residual), N, out.data_ptr(), N, M, N, K, code, splits, ws.data_ptr())
         return out
-    # The kernel addresses an operand with 32-bit byte offsets (buffer loads): A, and the residual, must stay below
-    # 2 GiB per call.  More rows than that (long clips of multi-scale token maps) go through in row ranges; every
-    # layout here is row-separable (strides are explicit arguments), so a range is the same call on offset pointers.
-    rows_max = (_GEMM_MAX_BYTES - 1) // (4 * max(K, N if residual is not None else 1))
+    # A, and the residual, must stay below 2 GiB per call: more rows than that (long clips of multi-scale token maps) go
+    # through in row ranges
     if x_blocked:
         _require(M * K * 4 < _GEMM_MAX_BYTES, "linear: a K-block-major x of 2 GiB or more is not supported")
-        rows_max = M
-    rows_max = max(128, rows_max // 128 * 128)
     out_row = int(col_block) if col_block else N            # elements a row advances the output pointer by
     with _on(x.device):
-        for r0 in range(0, M, rows_max):
-            r1 = min(M, r0 + rows_max)
+        for r0, r1 in _row_ranges(M, 4 * max(K, N if residual is not None else 1), rows_max=M if x_blocked else None):
             off = lambda t, per_row: 0 if t is None else t.data_ptr() + r0 * per_row * t.element_size()  # noqa: E731
-            _call("linear", "dfx_gemm_f32", x.device, off(x2, 4 if x_blocked else K), off(add, K), K, 0, weight.data_ptr(), K, 0, 0,
-                  _ptr(bias), 0, off(residual, N), N, 0, off(row_mask, 1), 0, off(out, out_row), N, 0, r1 - r0, N, K, 1,
-                  code, int(col_block), M * int(col_block), M * 4 if x_blocked else 0)
+            _gemm_f32("linear", x.device, off(x2, 4 if x_blocked else K), weight.data_ptr(), off(out, out_row), r1 - r0, N, K,
+                      K, K, N, A2=off(add, K), bias=_ptr(bias), R=off(residual, N), ldr=N, row_mask=off(row_mask, 1), relu=code,
+                      c_block=int(col_block), c_block_stride=M * int(col_block), a_block_stride=M * 4 if x_blocked else 0)
     return out
 
 
-_BF16_DTYPE_CODE = {torch.float32: 0, torch.bfloat16: 1}      # DFX_DT_* of include/dfx_gemm_bf16.h
+_BF16_DTYPE_CODE = {torch.float32: _C["DFX_DT_F32"], torch.bfloat16: _C["DFX_DT_BF16"]}
 
 
 def linear_bf16(x, weight_bf16, bias=None, act=None, residual=None, out_dtype=torch.float32):
@@ -796,12 +814,8 @@ def linear_bf16(x, weight_bf16, bias=None, act=None, residual=None, out_dtype=to
     if residual is not None:
         _require(residual.dtype == torch.float32 and residual.shape == out.shape, "linear_bf16: residual must be float32 and match the output")
     ea, ec = x2.element_size(), out.element_size()
-    # an operand of one call stays below 2 GiB (32-bit byte offsets): more rows go through in row ranges, as in linear()
-    rows_max = (_GEMM_MAX_BYTES - 1) // max(K * ea, N * ec, N * 4 if residual is not None else 1)
-    rows_max = max(128, rows_max // 128 * 128)
     a_code, c_code, code = _BF16_DTYPE_CODE[x2.dtype], _BF16_DTYPE_CODE[out_dtype], ACT[act]
-    for r0 in range(0, M, rows_max):
-        r1 = min(M, r0 + rows_max)
+    for r0, r1 in _row_ranges(M, max(K * ea, N * ec, N * 4 if residual is not None else 1)):
         _call("linear_bf16", "dfx_gemm_bf16", x.device, x2.data_ptr() + r0 * K * ea, a_code, K, weight_bf16.data_ptr(), K, _ptr(bias),
               0 if residual is None else residual.data_ptr() + r0 * N * 4, N, out.data_ptr() + r0 * N * ec, c_code, N,
               r1 - r0, N, K, code)
@@ -823,18 +837,22 @@ def _wgrad_ranges(M, splits):
     return kper, (M + kper - 1) // kper
 
 
+def _wgrad_tiles(N, K):
+    """(output tiles, workgroups of one resident round) of a weight gradient dW[N,K]: ceil(N / 128) * ceil(K / 128) tiles of
+    128 x 128 at 3 workgroups per CU, or, for N <= 64, one row of 64 x 128 tiles at 4 per CU."""
+    if N <= 64:
+        return -(-K // 128), 1024
+    return -(-N // 128) * -(-K // 128), 768
+
+
 def _wgrad_splits(M, N, K):
     """Number of row ranges of the weight gradient dW[N,K] = dY[M,N]^T x[M,K] (pure host rule, ``_split_k``'s): the output has
-    only ceil(N / 128) * ceil(K / 128) tiles (one 64-row tile for N <= 64), so the M rows are cut into as many ranges as keep
-    tiles x ranges within one resident round of workgroups (3 per CU for the 128 x 128 tile, 4 for the 64 x 128 one), each at
-    least ``_WGRAD_MIN_STEPS`` 16-row steps long, at most ``_WGRAD_MAX_RANGES`` of them.  The result is what the library
-    will run: no range is empty."""
+    only ``_wgrad_tiles`` tiles, so the M rows are cut into as many ranges as keep tiles x ranges within one resident round of
+    workgroups, each at least ``_WGRAD_MIN_STEPS`` 16-row steps long, at most ``_WGRAD_MAX_RANGES`` of them.  The result is
+    what the library will run: no range is empty."""
     if M <= 0:
         return 1
-    if N <= 64:
-        tiles, slots = -(-K // 128), 1024
-    else:
-        tiles, slots = -(-N // 128) * -(-K // 128), 768
+    tiles, slots = _wgrad_tiles(N, K)
     want = max(1, min(-(-M // 16) // _WGRAD_MIN_STEPS, slots // tiles, _WGRAD_MAX_RANGES, 65535))
     return _wgrad_ranges(M, want)[1]
 
@@ -858,11 +876,9 @@ def linear_backward(grad_out, x, weight, need_x=True, need_w=True, need_b=True, 
     grad_x = grad_w = grad_b = None
     if need_x:
         grad_x = torch.empty(x.shape, dtype=torch.float32, device=dev)
-        rows_max = max(128, (_GEMM_MAX_BYTES - 1) // (4 * max(N, K)) // 128 * 128)
-        for r0 in range(0, M, rows_max):
-            r1 = min(M, r0 + rows_max)
-            _call("linear_backward (grad_x)", "dfx_gemm_f32", dev, go.data_ptr() + r0 * N * 4, 0, N, 0, weight.data_ptr(), K, 0, 1,
-                  0, 0, 0, 0, 0, 0, 0, grad_x.data_ptr() + r0 * K * 4, K, 0, r1 - r0, K, N, 1, 0, 0, 0, 0)
+        for r0, r1 in _row_ranges(M, 4 * max(N, K)):
+            _gemm_f32("linear_backward (grad_x)", dev, go.data_ptr() + r0 * N * 4, weight.data_ptr(), grad_x.data_ptr() + r0 * K * 4,
+                      r1 - r0, K, N, N, K, K, b_is_kn=1)
     if need_w:
         grad_w = torch.empty((N, K), dtype=torch.float32, device=dev)
         grad_b = torch.empty((N,), dtype=torch.float32, device=dev) if need_b else None
@@ -923,8 +939,9 @@ def conv1x1(x, weight, bias=None, residual=None, relu=False, stride=1):
     out = torch.empty((Nb, Co, H, W), dtype=x.dtype, device=x.device)
     if residual is not None:
         _require(residual.shape == out.shape, "residual must match the output")
-    _call("conv1x1", "dfx_gemm_f32", x.device, w2.data_ptr(), 0, Ci, 0, x.data_ptr(), HW, Ci * HW, 1, _ptr(bias), 1,
-          _ptr(residual), HW, Co * HW, 0, 0, out.data_ptr(), HW, Co * HW, Co, HW, Ci, Nb, int(bool(relu)), 0, 0, 0)
+    _gemm_f32("conv1x1", x.device, w2.data_ptr(), x.data_ptr(), out.data_ptr(), Co, HW, Ci, Ci, HW, HW, strideB=Ci * HW, b_is_kn=1,
+              bias=_ptr(bias), bias_per_row=1, R=_ptr(residual), ldr=HW, strideR=Co * HW, strideC=Co * HW, batch=Nb,
+              relu=int(bool(relu)))
     return out
 
 
@@ -935,17 +952,13 @@ _conv1x1_forward = conv1x1
 
 def _conv1x1_wgrad_splits(Co, Ci, HW, batch):
     """Pixel ranges per image of the weight gradient dW[Co,Ci] = sum_n dZ[n] X[n]^T (pure host rule, ``_wgrad_splits``' with the
-    images as a second source of workgroups): tiles x images x ranges stay within one resident round of workgroups (3 per CU
-    for the 128 x 128 tile, 4 for the 64 x 128 one of Co <= 64), a range is at least ``_WGRAD_MIN_STEPS`` 16-deep steps long
-    and images x ranges stay within ``_WGRAD_MAX_RANGES`` slabs.  Both constants are taken over from ``_wgrad_splits`` as
-    they are; they were measured for Linear layers and not re-tuned for this product.  The result is what the library will
-    run: no range is empty."""
+    images as a second source of workgroups): ``_wgrad_tiles`` x images x ranges stay within one resident round of workgroups,
+    a range is at least ``_WGRAD_MIN_STEPS`` 16-deep steps long and images x ranges stay within ``_WGRAD_MAX_RANGES`` slabs.
+    Both constants are taken over from ``_wgrad_splits`` as they are; they were measured for Linear layers and not re-tuned
+    for this product.  The result is what the library will run: no range is empty."""
     if HW <= 0 or batch <= 0:
         return 1
-    if Co <= 64:
-        tiles, slots = -(-Ci // 128), 1024
-    else:
-        tiles, slots = -(-Co // 128) * -(-Ci // 128), 768
+    tiles, slots = _wgrad_tiles(Co, Ci)
     want = max(1, min(-(-HW // 16) // _WGRAD_MIN_STEPS, slots // (tiles * batch), _WGRAD_MAX_RANGES // batch))
     return _wgrad_ranges(HW, want)[1]
 
@@ -1085,7 +1098,7 @@ def _dynamic_conv_forward(feats, params, norm1, norm2):
     return out
 
 
-DYNCONV_BWD_WS_FLOATS = 256 * 640      # DFX_DYNCONV_BWD_WS_FLOATS of include/dfx_roi.h
+DYNCONV_BWD_WS_FLOATS = _C["DFX_DYNCONV_BWD_WS_FLOATS"]
 
 
 def dynamic_conv_backward(grad_out, feats, params, norm1, norm2, need_feats=True, need_params=True):
@@ -1285,7 +1298,7 @@ def add_layernorm(x, residual, norm):
     return out
 
 
-ADDLN_BWD_ROWS_PER_BLOCK, ADDLN_BWD_MAX_GRID = 16, 1024      # DFX_ADDLN_BWD_* of include/dfx_fused.h
+ADDLN_BWD_ROWS_PER_BLOCK, ADDLN_BWD_MAX_GRID = _C["DFX_ADDLN_BWD_ROWS_PER_BLOCK"], _C["DFX_ADDLN_BWD_MAX_GRID"]
 
 
 def add_layernorm_backward_grid(rows):
@@ -1533,7 +1546,7 @@ def _group_norm_forward(x, weight, bias, groups, eps, tokens_out):
     return y, stats
 
 
-GN_BWD_CHUNKS = 16      # DFX_GN_BWD_CHUNKS of include/dfx_fused.h
+GN_BWD_CHUNKS = _C["DFX_GN_BWD_CHUNKS"]
 
 
 def group_norm_backward(grad_out, x, stats, gamma, groups, tokens=False, need_x=True, need_gamma=True, need_beta=True):
@@ -1604,7 +1617,7 @@ def group_norm(x, norm, tokens_out=False):
 
 
 # ---- BatchNorm2d with batch statistics (+ GELU) in grad mode (include/dfx_fused.h, csrc/batchnorm_train.hip) --------------------
-BN_CHUNK_PIXELS = 8192      # DFX_BN_CHUNK_PIXELS of include/dfx_fused.h
+BN_CHUNK_PIXELS = _C["DFX_BN_CHUNK_PIXELS"]
 
 
 def _bn_partials(N, HW):

@@ -40,6 +40,110 @@ def test_python_binding_covers_the_header():
     assert set(declared_symbols()) <= bound
 
 
+_I, _L, _F, _D, _P = ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_double, ctypes.c_void_p
+# one entry point of every shape the header parser has to read, its types stated by hand from the header
+HAND_STATED = {
+    # A, A2, lda, strideA, B, ldb, strideB, b_is_kn, bias, bias_per_row, R, ldr, strideR, row_mask, strideMask, C, ldc, strideC,
+    # M, N, K, batch, relu, c_block, c_block_stride, a_block_stride, stream
+    "dfx_gemm_f32": (_I, [_P, _P, _L, _L, _P, _L, _L, _I, _P, _I, _P, _L, _L, _P, _L, _P, _L, _L,
+                          _I, _I, _I, _I, _I, _I, _L, _L, _P]),
+    "dfx_tuning_reload": (_I, []),                                                                    # (void)
+    # x, gamma, beta, running_mean, running_var, y, stats, workspace, N, C, HW, eps, momentum, act, stream: doubles
+    "dfx_batch_norm_train_f32": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _L, _D, _D, _I, _P]),
+    # input, rois, N, C, H, W, K, ph, pw, spatial_scale, sampling_ratio, aligned, out, stream: a float in the middle
+    "dfx_roi_align_nhwc_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _F, _I, _I, _P, _P]),
+    # value, ref, ref_dim, off, logits, layout (a struct pointer), N, H, W, Lq, out, stream
+    "dfx_msda_fused_level_forward_f32": (_I, [_P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
+    "dfx_last_error": (ctypes.c_char_p, []),                                                          # const char *(void)
+}
+
+
+@pytest.mark.parametrize("name", sorted(HAND_STATED))
+def test_binding_reads_the_hand_stated_types_from_the_header(name):
+    from dfx import _lib
+    restype, argtypes = HAND_STATED[name]
+    assert _lib.SIGNATURES[name] == argtypes
+    assert getattr(_lib.load(), name).restype is restype
+
+
+def test_loaded_library_carries_every_parsed_signature():
+    from dfx import _lib
+    lib = _lib.load()
+    assert set(_lib.SIGNATURES) == set(declared_symbols())
+    for name, argtypes in _lib.SIGNATURES.items():
+        fn = getattr(lib, name)
+        assert fn.argtypes == argtypes, name
+        assert fn.restype is (ctypes.c_char_p if name == "dfx_last_error" else ctypes.c_int), name
+
+
+def test_parser_refuses_what_it_does_not_know_by_name():
+    """A scalar type outside int / long / float / double, or a macro value that is no integer or product of integers, raises and
+    names the function and parameter, or the macro: nothing is guessed, nothing is silently left out."""
+    from dfx import _lib
+    for text, names in (("int dfx_x(short a, void *stream);", ("dfx_x", "short a")),
+                        ("int dfx_y(int n, unsigned int flags);", ("dfx_y", "unsigned int flags")),
+                        ("int dfx_z(int);", ("dfx_z", "int")),
+                        ("#define DFX_BAD (1 << 4)\n", ("DFX_BAD",)),
+                        ("#define DFX_SUM (2 + 3)\n", ("DFX_SUM",)),
+                        ("#define DFX_ALIAS DFX_OTHER\n", ("DFX_ALIAS",))):
+        with pytest.raises(RuntimeError) as err:
+            _lib.parse_header(text)
+        for name in names:
+            assert name in str(err.value), (text, str(err.value))
+    prototypes, constants = _lib.parse_header(
+        "/* int dfx_commented(short a); */\n#define DFX_GUARD_H\n#define DFX_FN(x) ((x) + 1)\n#define DFX_NEG (-7) /* why */\n"
+        "#define DFX_PROD (3 * 5)\n#define DFX_PLAIN 9\nconst char *dfx_s(void);\nint dfx_f(const long *p, double d,\n  long n);\n")
+    assert constants == {"DFX_NEG": -7, "DFX_PROD": 15, "DFX_PLAIN": 9}
+    assert prototypes == {"dfx_s": (ctypes.c_char_p, []), "dfx_f": (ctypes.c_int, [_P, _D, _L])}
+
+
+def test_constants_hold_every_integer_define_of_the_headers():
+    from dfx import _lib
+    assert _lib.CONSTANTS["DFX_DYNCONV_BWD_WS_FLOATS"] == 163840
+    assert _lib.CONSTANTS["DFX_ENONFINITE"] == -4 == _lib.ENONFINITE
+    hand_stated = {
+        "DFX_OK": 0, "DFX_EINVAL": -1, "DFX_ELAUNCH": -2, "DFX_ERANGE": -3, "DFX_ENONFINITE": -4,
+        "DFX_ACT_NONE": 0, "DFX_ACT_RELU": 1, "DFX_ACT_GELU": 2, "DFX_DT_F32": 0, "DFX_DT_BF16": 1,
+        "DFX_ADDLN_BWD_ROWS_PER_BLOCK": 16, "DFX_ADDLN_BWD_MAX_GRID": 1024, "DFX_GN_BWD_CHUNKS": 16,
+        "DFX_BN_CHUNK_PIXELS": 8192, "DFX_BN_BWD_MAX_GROUPS": 128, "DFX_OPTIM_CHUNK": 8192,
+        "DFX_DYNCONV_BWD_WS_FLOATS": 163840}
+    assert {k: _lib.CONSTANTS.get(k) for k in hand_stated} == hand_stated
+    # no value-carrying object-like macro of the headers is missing: names found here without the binding's parser
+    valued = []
+    for h in glob.glob(os.path.join(ROOT, "include", "*.h")):
+        valued += re.findall(r"^\s*#\s*define\s+(DFX_\w+)[ \t]+[-(\d]", open(h).read(), flags=re.M)
+    assert len(valued) >= len(hand_stated) and sorted(valued) == sorted(_lib.CONSTANTS)
+
+
+def test_ops_constants_are_the_headers():
+    from dfx import _lib, ops
+    c = _lib.CONSTANTS
+    assert ops.DYNCONV_BWD_WS_FLOATS == c["DFX_DYNCONV_BWD_WS_FLOATS"] and ops.GN_BWD_CHUNKS == c["DFX_GN_BWD_CHUNKS"]
+    assert (ops.ADDLN_BWD_ROWS_PER_BLOCK, ops.ADDLN_BWD_MAX_GRID) == (c["DFX_ADDLN_BWD_ROWS_PER_BLOCK"], c["DFX_ADDLN_BWD_MAX_GRID"])
+    assert ops.BN_CHUNK_PIXELS == c["DFX_BN_CHUNK_PIXELS"]
+    assert ops.ACT == {None: 0, "none": 0, "relu": 1, "gelu": 2}
+
+
+def test_gemm_helper_puts_every_argument_where_the_header_names_it(monkeypatch):
+    """ops._gemm_f32 takes the header's parameter names; each value must reach the position the prototype gives that name
+    (no launch: ops._call is replaced by a recorder)."""
+    import inspect
+    from dfx import ops
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "dfx_gemm.h")).read(), flags=re.S)
+    params = re.search(r"int dfx_gemm_f32\(([^)]*)\)", text).group(1).split(",")
+    names = [p.split()[-1].lstrip("*") for p in params][:-1]          # the stream is _call's to add
+    assert len(names) == 26 and names[0] == "A" and names[-1] == "a_block_stride"
+    helper = list(inspect.signature(ops._gemm_f32).parameters)
+    assert helper[:2] == ["what", "dev"] and sorted(helper[2:]) == sorted(names)
+    calls = []
+    monkeypatch.setattr(ops, "_call", lambda what, name, dev, *args: calls.append((what, name, dev, args)))
+    ops._gemm_f32("w", "d", **{n: 100 + i for i, n in enumerate(names)})
+    assert calls == [("w", "dfx_gemm_f32", "d", tuple(range(100, 126)))]
+    ops._gemm_f32("w", "d", 1, 2, 3, 4, 5, 6, 7, 8, 9)                # A, B, C, M, N, K, lda, ldb, ldc; the rest absent
+    given = dict(A=1, B=2, C=3, M=4, N=5, K=6, lda=7, ldb=8, ldc=9, batch=1)
+    assert calls[1][3] == tuple(given.get(n, 0) for n in names)
+
+
 def test_cpu_tensors_are_rejected_like_the_reference():
     """ms_deform_attn.h:38 - AT_ERROR("Not implemented on the CPU")."""
     import torch
