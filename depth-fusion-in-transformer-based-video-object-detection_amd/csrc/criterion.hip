@@ -202,13 +202,18 @@ __global__ __launch_bounds__(kLossThreads) void set_loss_forward_kernel(
 __device__ __forceinline__ void giou_loss_grad(const double *a, const double *b, double scale, double *grad)
 {
     double lo[2], hi[2], blo[2], bhi[2], iw[2], ew[2];
+    bool overlap[2];
 #pragma unroll
     for (int d = 0; d < 2; ++d) {
         lo[d] = a[d] - 0.5 * a[2 + d];
         hi[d] = a[d] + 0.5 * a[2 + d];
         blo[d] = b[d] - 0.5 * b[2 + d];
         bhi[d] = b[d] + 0.5 * b[2 + d];
-        iw[d] = fmax(fmin(hi[d], bhi[d]) - fmax(lo[d], blo[d]), 0.0);
+        const double raw = fmin(hi[d], bhi[d]) - fmax(lo[d], blo[d]);
+        // the clamp at 0 passes the gradient AT 0 as well, as the reference's clamp(min=0) does: a prediction of zero width
+        // between the target's edges has raw == 0, and the intersection grows with its width at the rate of the other side
+        overlap[d] = raw >= 0.0;
+        iw[d] = fmax(raw, 0.0);
         ew[d] = fmax(fmax(hi[d], bhi[d]) - fmin(lo[d], blo[d]), 0.0);
     }
     const double side[2] = {hi[0] - lo[0], hi[1] - lo[1]};
@@ -224,7 +229,7 @@ __device__ __forceinline__ void giou_loss_grad(const double *a, const double *b,
     for (int d = 0; d < 2; ++d) {
         const int o = 1 - d;
         double g_lo = -g_area * side[o], g_hi = g_area * side[o];
-        const double g_iw = iw[d] > 0.0 ? g_inter * iw[o] : 0.0;          // through the clamp at 0
+        const double g_iw = overlap[d] ? g_inter * iw[o] : 0.0;            // through the clamp at 0
         if (lo[d] > blo[d]) g_lo -= g_iw;                                  // max(lo, blo)
         if (hi[d] < bhi[d]) g_hi += g_iw;                                  // min(hi, bhi)
         const double g_ew = ew[d] > 0.0 ? g_enc * ew[o] : 0.0;

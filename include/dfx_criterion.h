@@ -58,7 +58,9 @@ int dfx_set_loss_forward_f32(const float *logits, const float *boxes, const int 
  * columns 0, 2 and 3 are read.  grad_logits [rows, 3] and grad_boxes [rows, 4] are written in full; either may be NULL.
  * Column 0 of grad_logits and the box gradient of unmatched rows are exactly zero.  Where two box edges coincide exactly,
  * the max / min inside GIoU hands the whole gradient to the target's side (autograd splits it in two): a set of measure
- * zero on which the sub-gradient is not unique. */
+ * zero on which the sub-gradient is not unique.  The clamp of the intersection's extent at 0 passes the gradient at exactly 0
+ * too, as the reference's clamp(min=0) does: a prediction of zero width between the target's edges gets the derivative of
+ * the intersection in its width, the only one there is on w >= 0. */
 int dfx_set_loss_backward_f32(const float *grad_out, const float *logits, const float *boxes, const int *tgt_labels,
                               const float *tgt_boxes, const int *row_target, const int *desc, int S, int B, int rows,
                               int Ttot, double inv_num_boxes, float *grad_logits, float *grad_boxes, void *stream);

@@ -180,3 +180,111 @@ def test_build_model_returns_a_working_criterion(golden_dir):
     for t in (logits, boxes, aux_l, aux_b):
         assert t.grad is not None and torch.isfinite(t.grad).all() and t.grad.abs().sum() > 0
     assert not losses["cardinality_error"].requires_grad and not losses["class_error"].requires_grad
+
+
+# ---- the hand-built families of tests/_criterion_cases.py: what their names claim, computed in fp64 ----------------------
+def _built_pairs(layout="dense"):
+    fam = cc.giou_family(layout)
+    rows = fam["indices"][0][0].tolist()
+    return [(n, fam["boxes"][0, r], fam["targets"][0][1][k]) for k, (n, r) in enumerate(zip(fam["names"], rows))]
+
+
+def test_giou_configurations_have_the_property_their_name_claims():
+    """on the fp32-representable values the kernels are given: no edge of a prediction coincides with an edge of its target,
+    no coordinate equals the target's, sides are at least 0.01 unless zero is the point, and each kind is what it says"""
+    kinds = set()
+    pairs = _built_pairs()
+    assert [n for n, _, _ in pairs] == list(cc.GIOU_CONFIGS)
+    for name, pred, tgt in pairs:
+        kind = cc.GIOU_CONFIGS[name][0]
+        kinds.add(kind)
+        f = cc.giou_facts(pred, tgt)
+        rx, ry = f["raw"]
+        assert f["coincidences"] == 0 and f["target_area"] > 0 and f["enclosure"] > 0, name
+        assert all(s >= 0.01 or (s == 0 and kind.startswith("zero")) for s in f["sides"]), name
+        if kind in ("partial", "corner"):
+            assert rx > 0 and ry > 0 and 0 < f["inter"] < min(f["area"], f["target_area"]), name
+            assert not f["pred_inside"] and not f["target_inside"], name
+            assert (f["inter"] < 0.05 * f["area"]) == (kind == "corner"), name
+        elif kind == "disjoint_x":
+            assert rx < 0 < ry and f["inter"] == 0, name
+        elif kind == "disjoint_y":
+            assert ry < 0 < rx and f["inter"] == 0, name
+        elif kind == "disjoint_both":
+            assert rx < 0 and ry < 0 and f["inter"] == 0, name
+        elif kind == "pred_inside":
+            assert f["pred_inside"] and f["area"] > 0 and f["inter"] == pytest.approx(f["area"], rel=1e-12), name
+        elif kind == "target_inside":
+            assert f["target_inside"] and f["inter"] == pytest.approx(f["target_area"], rel=1e-12), name
+        elif kind == "zero_side_inside":
+            assert f["pred_inside"] and f["area"] == 0 and f["inter"] == 0 and sorted(f["sides"])[0] == 0 < sorted(f["sides"])[1], name
+            assert min(rx, ry) == 0 < max(rx, ry), name
+        elif kind == "zero_side_straddling":
+            assert not f["pred_inside"] and f["area"] == 0 and f["inter"] == 0 and min(rx, ry) == 0, name
+            assert 0 < max(rx, ry) < max(f["sides"]), name           # the other axis overlaps in part
+        elif kind == "zero_area_away":
+            assert f["sides"] == [0, 0] and min(rx, ry) < 0 and f["inter"] == 0, name
+        elif kind == "far_apart":
+            assert rx < -0.8 and ry < -0.8 and f["enclosure"] > 100 * (f["area"] + f["target_area"]), name
+        else:
+            raise AssertionError(f"{name}: unknown kind {kind}")
+    assert kinds == {"partial", "corner", "disjoint_x", "disjoint_y", "disjoint_both", "pred_inside", "target_inside",
+                     "zero_side_inside", "zero_side_straddling", "zero_area_away", "far_apart"}
+    # both axis orders and both sides of every max / min: which edge of the prediction lies beyond the target's, per axis
+    sides = {(d, bool(p[d] - 0.5 * p[2 + d] < t[d] - 0.5 * t[2 + d]), bool(p[d] + 0.5 * p[2 + d] > t[d] + 0.5 * t[2 + d]))
+             for _, p, t in pairs for d in range(2)}
+    assert sides == {(d, lo, hi) for d in range(2) for lo in (False, True) for hi in (False, True)}
+
+
+def test_spread_layout_puts_the_pairs_in_every_wave_of_every_pass():
+    """1100 rows under 512 threads: passes at 0, 512, 1024, waves of 64 lanes - 18 (pass, wave) slots, each with two matched
+    rows; every configuration appears, with the dense layout's boxes"""
+    fam = cc.giou_family("spread")
+    rows = fam["indices"][0][0].tolist()
+    assert fam["logits"].shape == (1, cc.SPREAD_Q, 3) and len(set(rows)) == len(rows) == 36 and max(rows) == cc.SPREAD_Q - 1
+    slots = {}
+    for r in rows:
+        slots.setdefault((r // 512, (r % 512) // 64), []).append(r)
+    assert sorted(slots) == [(p, w) for p in range(2) for w in range(8)] + [(2, 0), (2, 1)] and all(len(v) == 2 for v in slots.values())
+    assert set(fam["names"]) == set(cc.GIOU_CONFIGS)
+    dense = {n: (p, t) for n, p, t in _built_pairs("dense")}
+    for n, p, t in _built_pairs("spread"):
+        assert torch.equal(p, dense[n][0]) and torch.equal(t, dense[n][1]), n
+
+
+def test_saturated_family_uses_every_value_in_every_role():
+    fam = cc.saturated_family()
+    logits, (matched, cols) = fam["logits"][0], fam["indices"][0]
+    labels = fam["targets"][0][0][cols]
+    role = torch.full((logits.shape[0],), 2)
+    role[matched] = torch.where(labels == 1, 0, 1)
+    values = sorted(torch.tensor(cc.SATURATED, dtype=torch.float32).double().tolist())
+    assert len(values) == 15 and 1e4 in values and -1e4 in values
+    plain = torch.arange(logits.shape[0]) < 3 * len(values)
+    for r in range(3):
+        for c in (1, 2):
+            assert sorted(logits[plain & (role == r), c].tolist()) == values, (r, c)
+        assert (role[~plain] == r).sum() == len(cc.TIE_ROWS)
+    assert set(labels[role[matched] == 1].tolist()) == {0, 2}
+    ties = logits[~plain]
+    top = ties.max(-1, keepdim=True).values
+    assert ((ties == top).sum(-1) >= 2).all()
+    assert ((ties[:, 0] == top[:, 0]) & (ties[:, 1] == top[:, 0])).any() and ((ties[:, 1] == top[:, 0]) & (ties[:, 2] == top[:, 0]) & (ties[:, 0] < top[:, 0])).any()
+
+
+@pytest.mark.parametrize("builder,args", [(cc.giou_family, ("dense",)), (cc.giou_family, ("spread",)), (cc.saturated_family, ()),
+                                          (cc.bad_label_family, ())])
+def test_family_references_are_finite_and_their_fp32_run_is_a_rounding(builder, args):
+    """the fp64 torch formulation the GPU tests compare with, and the same in fp32 (evaluated in fp64, rounded once): within a
+    few ulp of it relative to each tensor's largest magnitude"""
+    ref = cc.family_reference_fp64(builder, *args)
+    f32 = cc.family_reference(builder(*args), torch.float32)
+    for a, b in zip(ref[0] + ref[1:], f32[0] + f32[1:]):
+        assert torch.isfinite(a).all() and torch.isfinite(b).all()
+        assert cc.rel_err(b, a) <= 4 * cc.HALF_ULP
+
+
+def test_wide_cost_inputs_reach_the_saturated_log():
+    logits, boxes, targets = cc.wide_cost_inputs()
+    assert logits.shape == (2, 40, 3) and [len(l) for l, _ in targets] == [3, 9]
+    assert logits.max() > 11 and logits.min() < -11 and torch.equal(logits, logits.float().double())
