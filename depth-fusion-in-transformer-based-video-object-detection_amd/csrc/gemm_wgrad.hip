@@ -16,10 +16,12 @@
 #include "dfx_common.h"
 #include "dfx_gemm.h"
 #include "mfma_tile.h"
+#include "wgrad_reduce.h"
 
 namespace {
 
 using namespace dfx::mfma;
+using dfx::wgrad_reduce_kernel;      // (wgrad_reduce.h: shared with gemm_bf16_wgrad.hip)
 
 struct WgradArgs {
     const float *dY = nullptr, *X = nullptr;
@@ -168,25 +170,6 @@ __global__ __launch_bounds__(256, BM == 128 ? 3 : 4) void gemm_wgrad_kernel(cons
     e.M = g.N, e.N = g.K;
     const f32x4 none[1] = {{0.f, 0.f, 0.f, 0.f}};
     epilogue_lean<T, 0, false, false, false>(smem, acc, l, m0, n0, e, none, false);
-}
-
-// dW = sum_s slab_s, db = sum_s db row_s, ascending s (splits = 0: zeros); float4 per thread, the db quads follow the dW quads
-__global__ void wgrad_reduce_kernel(const float *ws, int splits, long slab, long NK, int N, int K, float *dW, long ldw, float *db)
-{
-    const long e = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
-    float *dst;
-    if (e < NK) {
-        const long n = e / K;
-        dst = dW + n * ldw + (e - n * K);
-    } else if (db && e < NK + N) {
-        dst = db + (e - NK);
-    } else {
-        return;
-    }
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (splits > 0) v = *reinterpret_cast<const f32x4 *>(ws + e);
-    for (int s = 1; s < splits; ++s) v += *reinterpret_cast<const f32x4 *>(ws + (long)s * slab + e);
-    dst[0] = v[0], dst[1] = v[1], dst[2] = v[2], dst[3] = v[3];
 }
 
 }  // namespace

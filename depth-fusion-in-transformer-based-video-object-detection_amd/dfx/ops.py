@@ -923,6 +923,110 @@ def linear_train(x, weight, bias=None):
     return linear(x, weight, bias)
 
 
+# ---- Linear in grad mode on bf16 products (include/dfx_gemm_bf16.h, dfx_gemm_bf16_wgrad; csrc/gemm_bf16_wgrad.hip) ----------------
+def _wgrad_bf16_ranges(M, splits):
+    """(rows per range, ranges) ``dfx_gemm_bf16_wgrad`` makes of a request for ``splits`` ranges over M rows: whole 32-row steps,
+    none empty."""
+    kper = ((M + splits - 1) // splits + 31) // 32 * 32
+    return kper, (M + kper - 1) // kper
+
+
+# The split rule's constants for this kernel, measured (tools/bench_linear_bf16_train.py --ranges, profiles/r22_linear_bf16_train.txt).
+# The kernel moves a range two to three times faster than the fp32 one, so the reduction's traffic weighs more and fewer, longer
+# ranges win: tiles x ranges within 512 workgroups (two per CU) and at most 64 ranges are within 5 % of the best count at every
+# shape tried (32 x 4200 rows: 256 -> 1024 177 us at 32 ranges against 193 at 48 and 213 at 64; 256 -> 256 90 us at 64, 87 at 96,
+# 111 at 191; 256 -> 64 64 us at 64, 61 at 96, 101 at 248).  The shortest range stays ``_WGRAD_MIN_STEPS`` = 16 steps, here of 32
+# rows: at 9600 and 4 x 4200 rows 16-step ranges are the best or within 2 % of it, 32-step ranges are 8-19 % behind.
+_WGRAD_BF16_SLOTS = 512
+_WGRAD_BF16_MAX_RANGES = 64
+
+
+def _wgrad_bf16_splits(M, N, K):
+    """Number of row ranges of the bf16 weight gradient: ``_wgrad_splits``' rule restated for this kernel's 32-row step, with
+    ``_wgrad_tiles``' tiles (128 x 128, or 64 x 128 for N <= 64) and the constants above.  The result is what the library will
+    run: no range is empty."""
+    if M <= 0:
+        return 1
+    tiles = _wgrad_tiles(N, K)[0]
+    want = max(1, min(-(-M // 32) // _WGRAD_MIN_STEPS, _WGRAD_BF16_SLOTS // tiles, _WGRAD_BF16_MAX_RANGES, 65535))
+    return _wgrad_bf16_ranges(M, want)[1]
+
+
+def linear_bf16_backward(grad_out, x, weight_t_bf16, need_x=True, need_w=True, need_b=True, splits=None):
+    """Gradients of ``y = linear_bf16(x, weight_bf16, bias)`` on bf16 products with fp32 accumulation:
+    -> (grad_x | None, grad_w | None, grad_b | None), fp32, fresh tensors.
+    grad_out [..., N] and x [..., K] fp32 contiguous; weight_t_bf16 [K, N] bf16 contiguous, the transpose of the layer's bf16
+    weight; N and K multiples of 8.
+    grad_x = grad_out @ W is ``linear_bf16(grad_out, weight_t_bf16)``: the forward kernel with the transposed copy as its
+    [N', K'] operand, grad_out rounded to bf16 while it is staged, in ``linear_bf16``'s row ranges.  grad_w = grad_out^T @ x
+    (both rounded to bf16 while they are staged) and grad_b = grad_out.sum(0) (of the unrounded values) come from one
+    ``dfx_gemm_bf16_wgrad`` call, split over the rows by ``_wgrad_bf16_splits`` or ``splits``; partial sums are added in a fixed
+    order: two calls give the same bits.  ``need_w=False`` makes no weight-gradient launch; a bias gradient on its own is
+    ``grad_out.sum(0)`` of the library."""
+    _require(weight_t_bf16.dim() == 2, "linear_bf16_backward: weight_t_bf16 must be [K, N]")
+    K, N = weight_t_bf16.shape
+    _require(weight_t_bf16.dtype == torch.bfloat16, "linear_bf16_backward: the transposed weight copy must be bfloat16")
+    _require(grad_out.dtype == torch.float32 and x.dtype == torch.float32, "linear_bf16_backward: grad_out and x must be float32")
+    _require(N % 8 == 0 and K % 8 == 0 and N > 0 and K > 0, "linear_bf16_backward: N and K must be multiples of 8")
+    _require(grad_out.shape[-1] == N and x.shape[-1] == K, "linear_bf16_backward: grad_out [M,N], x [M,K], weight_t_bf16 [K,N]")
+    go, x2 = grad_out.reshape(-1, N), x.reshape(-1, K)
+    M = go.shape[0]
+    _require(x2.shape[0] == M, "linear_bf16_backward: grad_out and x must have the same rows")
+    _check_inputs([("grad_out", go), ("x", x2), ("weight_t_bf16", weight_t_bf16)])
+    dev = x.device
+    grad_x = grad_w = grad_b = None
+    if need_x:
+        grad_x = linear_bf16(go, weight_t_bf16).reshape(x.shape)
+    if need_w:
+        grad_w = torch.empty((N, K), dtype=torch.float32, device=dev)
+        grad_b = torch.empty((N,), dtype=torch.float32, device=dev) if need_b else None
+        n = _wgrad_bf16_splits(M, N, K) if splits is None else int(splits)
+        ws = torch.empty((n * (N * K + N),), dtype=torch.float32, device=dev) if n > 1 else None
+        _call("linear_bf16_backward (grad_w)", "dfx_gemm_bf16_wgrad", dev, go.data_ptr(), N, x2.data_ptr(), K, grad_w.data_ptr(), K,
+              _ptr(grad_b), M, N, K, n, _ptr(ws))
+    elif need_b:
+        grad_b = go.sum(0)
+    return grad_x, grad_w, grad_b
+
+
+_linear_bf16_forward = linear_bf16      # (bound for the node, as ``_linear_forward`` is)
+
+
+class _LinearBf16Function(torch.autograd.Function):
+    """apply(x, weight, bias | None, weight_bf16, weight_t_bf16): saves the contiguous fp32 x and the transposed bf16 copy.
+    ``weight`` is an input only to receive its gradient; the products read the two bf16 copies."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, weight_bf16, weight_t_bf16):
+        ctx.save_for_backward(x, weight_t_bf16)
+        return _linear_bf16_forward(x, weight_bf16, bias)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        x, weight_t_bf16 = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        # (looked up at call time: tests wrap it)
+        gx, gw, gb = linear_bf16_backward(grad_output.contiguous(), x, weight_t_bf16, need_x=need[0], need_w=need[1], need_b=need[2])
+        return gx, gw, gb, None, None
+
+
+def linear_bf16_train(x, weight, bias, weight_bf16, weight_t_bf16):
+    """``linear_bf16(x, weight_bf16, bias)`` (fp32 in, fp32 out) that trains ``weight`` [N, K] fp32, of which ``weight_bf16``
+    [N, K] and ``weight_t_bf16`` [K, N] are the caller's bf16 copies (models.fused.bf16_weight_pair): with grad mode on and x,
+    weight or bias requiring a gradient the result carries it back through ``linear_bf16_backward`` - computed for exactly the
+    inputs that ask for one, the weight's as fp32 in ``weight``'s shape; otherwise no autograd node is made.  Either way the
+    forward is ``linear_bf16`` itself (the same bits).  N and K multiples of 8."""
+    if torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad or (bias is not None and bias.requires_grad)):
+        N, K = weight.shape
+        _require(N % 8 == 0 and K % 8 == 0, "linear_bf16_train: N and K must be multiples of 8")
+        _require(weight_bf16.shape == (N, K) and weight_t_bf16.shape == (K, N) and weight_t_bf16.dtype == torch.bfloat16
+                 and weight_t_bf16.is_contiguous(), "linear_bf16_train: weight_bf16 [N,K] and a contiguous bf16 weight_t_bf16 [K,N]")
+        _require(x.dtype == torch.float32, "linear_bf16_train: x must be float32")
+        return _LinearBf16Function.apply(x.contiguous(), weight, bias, weight_bf16, weight_t_bf16)
+    return linear_bf16(x, weight_bf16, bias)
+
+
 def conv1x1(x, weight, bias=None, residual=None, relu=False, stride=1):
     """1x1 convolution on NCHW as a batched GEMM W[Co,Ci] x X_n[Ci,HW] with the folded-BN bias,
     the residual add and ReLU fused into the epilogue.  x [N,Ci,H,W], weight [Co,Ci(,1,1)]."""

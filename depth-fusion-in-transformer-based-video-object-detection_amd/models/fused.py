@@ -80,6 +80,27 @@ LINEAR_BF16 = os.environ.get("DFX_LINEAR_BF16", "0") == "1"
 # 112 -> 42.5 us at 9600 (2.64x), 50.2 -> 41.6 us at 300 (1.21x: host time there) - and so did the single-Linear GELU FFN of the
 # fusion layers (262 -> 157 us at 32 x 4200, 44 -> 28 us at 4 x 4200) (tools/bench_ffn_bf16.py, profiles/r21_ffn_bf16.txt).
 
+# Linear in grad mode on bf16 products with fp32 accumulation (dfx.ops.linear_bf16_train: the forward and the input gradient on
+# csrc/gemm_bf16.hip, the weight and bias gradients on csrc/gemm_bf16_wgrad.hip), fp32 tensors in and out of every layer.  OFF by
+# default: it changes the results (x, the weight and the incoming gradient are rounded to 8 significant bits inside the three
+# products; DESIGN.md 4l has the bounds).  DFX_LINEAR_BF16_TRAIN=1 turns it on.  Read once at import, consulted by
+# Linear.forward at call time; independent of LINEAR_BF16 (which is for no_grad).  Taken where ops.linear_train is taken today
+# when in_features and out_features are multiples of 8, out_features <= LINEAR_TRAIN_MAX_OUT_FEATURES and the call is large
+# enough (below).
+LINEAR_BF16_TRAIN = os.environ.get("DFX_LINEAR_BF16_TRAIN", "0") == "1"
+# The smallest call the route takes, in elements of the layer's input and output together, rows x (in_features + out_features):
+# the fp32 traffic that each of the three memory-bound products moves.  It is the smallest call that MEASURED faster than the
+# fp32 route beyond the repetition spread in both runs of tools/bench_linear_bf16_train.py (profiles/r22_linear_bf16_train.txt;
+# forward + backward of one layer, run A / run B): 12 x 4200 rows of 256 -> 64, 144 -> 97 us (1.48x) / 144 -> 100 us (1.44x).
+# Every larger call won in both runs: 32 x 4200 rows 1722 -> 632 us (2.72x / 2.71x) at 256 -> 1024, 541 -> 241 us (2.25x / 2.21x)
+# at 256 -> 256, 208 -> 127 us (1.64x / 1.63x) at 256 -> 32; 12 x 4200 rows 705 -> 272 us (2.59x / 2.56x) at 256 -> 1024,
+# 258 -> 102 us (2.54x / 2.46x) at 256 -> 256; 4 x 4200 rows of 256 -> 1024 285 -> 226 us (1.26x) / 278 -> 98 us (2.82x).
+# Below it a pass is host time - 90 us on a quiet host, 200 - 230 us on a busy one, whatever the route - and this route's Python
+# node costs ~5 us more of it: 0.91x - 0.98x, inside the spread, at 300 and 9600 rows at every width and at 4 x 4200 rows of
+# 256 -> 64 / 32; 12 x 4200 rows of 256 -> 32 0.94x / 1.24x and 4 x 4200 rows of 256 -> 256 0.94x / 1.54x, inside the spread both
+# times.  Those keep the fp32 route.
+LINEAR_BF16_TRAIN_MIN_ELEMENTS = 12 * 4200 * (256 + 64)
+
 
 def derived_key(*sources):
     """The "have the sources changed" key of every tensor kept by an inference route that was DERIVED from weights (folded BN,
@@ -109,7 +130,7 @@ DERIVED_ATTRIBUTES = ("_folded", "_plans1x1", "_chain_carry", "_stem_folded",   
 
 # ... and the one the opt-in bf16 FFN route keeps (bf16_weight below).  A tuple of its own: tests/test_weight_updates_cpu.py plants
 # exactly the names above and pins their number; drop_derived walks both.
-DERIVED_ATTRIBUTES_BF16 = ("_weight_bf16",)
+DERIVED_ATTRIBUTES_BF16 = ("_weight_bf16", "_weight_bf16_pair")      # bf16_weight, bf16_weight_pair
 
 
 def drop_derived(model):
@@ -142,6 +163,22 @@ def bf16_weight(linear):
     return kept[1]
 
 
+def bf16_weight_pair(linear):
+    """The two bf16 copies of a Linear's weight for the LINEAR_BF16_TRAIN route, made together: ([out_features, in_features],
+    [in_features, out_features]), both contiguous - the forward's operand and, transposed, the input gradient's.  One rounding
+    (``weight.to(torch.bfloat16)``), so the two hold the same values.  Kept on the module (DERIVED_ATTRIBUTES_BF16, a name of
+    its own: ``_weight_bf16`` belongs to the no_grad route) under ``derived_key(weight)`` plus the device and rebuilt when
+    that key changes - after every optimizer step; ``drop_derived`` forgets them."""
+    w = linear.weight
+    key = (derived_key(w), w.device)
+    kept = linear.__dict__.get("_weight_bf16_pair")
+    if kept is None or kept[0] != key:
+        wb = w.detach().to(torch.bfloat16).contiguous()
+        kept = (key, wb, wb.t().contiguous())
+        linear._weight_bf16_pair = kept
+    return kept[1], kept[2]
+
+
 def linear_bf16_usable(x, *linears):
     """May the FFN whose Linears are ``linears`` run on dfx.ops.linear_bf16 for the input ``x``?  Only as the LINEAR_BF16 comment
     says.  (The switch is read here, at call time, from this module's globals.)"""
@@ -168,8 +205,9 @@ class Linear(nn.Linear):
     """nn.Linear (same parameters, same state_dict keys) whose fp32 forward on the GPU is the hand-written MFMA GEMM with the
     bias in its epilogue (dfx.ops.linear, csrc/gemm_f32.hip).  In grad mode, when the input or a parameter asks for a
     gradient and out_features is a multiple of 4 (up to LINEAR_TRAIN_MAX_OUT_FEATURES) as well, the same forward carries an autograd node whose backward is the
-    GEMM again (input gradient) and csrc/gemm_wgrad.hip (weight and bias gradients): dfx.ops.linear_train.  Anything else
-    is nn.Linear."""
+    GEMM again (input gradient) and csrc/gemm_wgrad.hip (weight and bias gradients): dfx.ops.linear_train - or, with
+    LINEAR_BF16_TRAIN on, both feature counts multiples of 8 and LINEAR_BF16_TRAIN_MIN_ELEMENTS met, the same three products on bf16 operands:
+    dfx.ops.linear_bf16_train.  Anything else is nn.Linear."""
 
     def forward(self, x):
         # (under autocast, or with parameters in another dtype / on another device, this is plain nn.Linear)
@@ -182,6 +220,10 @@ class Linear(nn.Linear):
             if (LINEAR_TRAIN and self.out_features % 4 == 0 and self.out_features <= LINEAR_TRAIN_MAX_OUT_FEATURES
                     and (x.requires_grad or self.weight.requires_grad or (self.bias is not None and self.bias.requires_grad))):
                 from dfx import ops
+                if (LINEAR_BF16_TRAIN and self.in_features % 8 == 0 and self.out_features % 8 == 0
+                        and x.numel() // self.in_features * (self.in_features + self.out_features) >= LINEAR_BF16_TRAIN_MIN_ELEMENTS
+                        and (self.bias is None or (self.bias.dtype == torch.float32 and self.bias.device == x.device))):
+                    return ops.linear_bf16_train(x, self.weight, self.bias, *bf16_weight_pair(self))
                 return ops.linear_train(x, self.weight, self.bias)
         return super().forward(x)
 

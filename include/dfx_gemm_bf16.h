@@ -41,6 +41,29 @@ int dfx_gemm_bf16(const void *A, int a_dtype, long lda,
                   void *C, int c_dtype, long ldc,
                   int M, int N, int K, int act, void *stream);
 
+/*
+ * The weight gradient of a Linear that trains on bf16 products (csrc/gemm_bf16_wgrad.hip; dfx.ops.linear_bf16_backward;
+ * models.fused.LINEAR_BF16_TRAIN):
+ *
+ *   dW[n][k] = sum_m bf16(dY[m][n]) * bf16(X[m][k])      [N, K] fp32, row pitch ldw
+ *   db[n]    = sum_m dY[m][n]                            [N] fp32, from the UNROUNDED fp32 values; NULL: not computed
+ *
+ * dY [M,N] and X [M,K] are fp32, row-major, row pitches ldy and ldx in elements.  Both are rounded to bf16 (round-to-nearest-even)
+ * while they are staged; no bf16 copy of either is written to memory.  Products are exact, accumulation is fp32.
+ *
+ * M is cut into `splits` ranges of whole 32-row steps (clamped so that no range is empty), exactly as dfx_gemm_wgrad_f32
+ * (dfx_gemm.h) cuts it into 16-row steps.  Each range writes a partial slab to the caller-owned `workspace` of
+ * splits * (N*K + N) floats and one reduction launch adds the slabs in ascending range order: no atomics, two calls give the
+ * same bits.  One range stores directly, and `workspace` may then be NULL.  Outputs are overwritten, never accumulated into.
+ *
+ * DFX_EINVAL for negative dimensions or splits < 1, null pointers, N or K not multiples of 8, ldy / ldx / ldw not multiples of 4
+ * or shorter than the row, dY / X / dW / workspace not 16-byte aligned, more than one range without a workspace; DFX_ERANGE
+ * when dW, or one range of dY or X, reaches 2 GiB - all before any launch, with a dfx_last_error() text.  N*K == 0 returns
+ * DFX_OK without a launch; M == 0 writes zeros.  An addition to the ABI: dfx_abi_version() stays.
+ */
+int dfx_gemm_bf16_wgrad(const float *dY, long ldy, const float *X, long ldx, float *dW, long ldw,
+                        float *db, int M, int N, int K, int splits, float *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,6 +5,7 @@ torch routes and on dfx.optim.AdamW (csrc/optim.hip), and the two kernels' achie
     python tools/bench_optim_step.py --kernels             # the two kernels alone, back to back: bytes per second
     python tools/bench_optim_step.py --train-step          # one whole training step of the single-frame Late Fusion recipe at
                                                            # 2 x 800 x 1333 (bench_criterion.py --train-step) + the optimizer step
+                                                           # (DFX_LINEAR_BF16_TRAIN=1 [--linear-bf16-min-elements 0]: DESIGN.md 4l)
 
 Parameter sets: the trainable parameters of the single-frame Late Fusion recipe (LateFusion.sh: the RGB body frozen by the
 reference's group rules) and of TransVOD++ with depth (TransVOD++_withdepth.sh), grouped by models.optim.build_param_groups
@@ -154,9 +155,15 @@ def time_kernels(name, launches, repeats):
               f"{rate / 1e12:.2f} TB/s = {rate / HBM_BYTES_PER_S:.2f} of 8 TB/s")
 
 
-def train_step(repeats, warmup):
-    """bench_criterion.py --train-step with the optimizer step appended: forward, criterion, backward, clip + AdamW"""
+def train_step(repeats, warmup, bf16_min_elements=None):
+    """bench_criterion.py --train-step with the optimizer step appended: forward, criterion, backward, clip + AdamW.
+    bf16_min_elements: replaces models.fused.LINEAR_BF16_TRAIN_MIN_ELEMENTS (0: every eligible Linear takes the bf16 train route
+    when DFX_LINEAR_BF16_TRAIN=1, whatever its size - the step at 2 frames lies below the rule)."""
     import bench_criterion as bc
+    if bf16_min_elements is not None:
+        from models import fused
+        fused.LINEAR_BF16_TRAIN_MIN_ELEMENTS = bf16_min_elements
+        print(f"models.fused.LINEAR_BF16_TRAIN_MIN_ELEMENTS = {bf16_min_elements}")
     from dfx.optim import AdamW
     from models import build_model
     from util.misc import NestedTensor
@@ -186,7 +193,11 @@ def train_step(repeats, warmup):
             model.zero_grad(set_to_none=True)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            bc.one_call(crit, model(x), targets)
+            losses = bc.one_call(crit, model(x), targets)
+            if i == 0 and r == "none":      # the first pass: initial weights, the seed's dropout masks - comparable between runs
+                total = sum(losses[k] * crit.weight_dict[k] for k in losses if k in crit.weight_dict).item()
+                print(f"first pass (DFX_LINEAR_BF16_TRAIN={os.environ.get('DFX_LINEAR_BF16_TRAIN', '0')}): weighted loss {total:.6f}; "
+                      + ", ".join(f"{k} {losses[k].item():.6f}" for k in ("loss_ce", "loss_bbox", "loss_giou") if k in losses))
             if r == "dfx":
                 opt.step(max_norm=max_norm)
             elif opt is not None:
@@ -209,10 +220,11 @@ def main():
     ap.add_argument("--kernels", action="store_true")
     ap.add_argument("--launches", type=int, default=10)
     ap.add_argument("--train-step", action="store_true")
+    ap.add_argument("--linear-bf16-min-elements", type=int, default=None, help="with --train-step: override the bf16 train route's size rule")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_optim_step.py measures on the GPU; there is no CPU timing"
     if args.train_step:
-        return train_step(min(args.repeats, 5), min(args.warmup, 2))
+        return train_step(min(args.repeats, 5), min(args.warmup, 2), args.linear_bf16_min_elements)
     for name in (SETS if args.set == "all" else [args.set]):
         if args.kernels:
             time_kernels(name, args.launches, min(args.repeats, 10))
