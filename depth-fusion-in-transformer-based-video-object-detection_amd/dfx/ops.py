@@ -822,18 +822,28 @@ def linear_bf16(x, weight_bf16, bias=None, act=None, residual=None, out_dtype=to
     return out
 
 
-# ---- Linear in grad mode (include/dfx_gemm.h, dfx_gemm_wgrad_f32; csrc/gemm_wgrad.hip) ------------------------------------------
-# The split rule's two constants, both measured (tools/bench_linear_train.py, profiles/r14_linear_train.txt): ranges of at
+# ---- Linear in grad mode (include/dfx_gemm.h dfx_gemm_wgrad_f32, include/dfx_gemm_bf16.h dfx_gemm_bf16_wgrad; csrc/wgrad_frame.h) ----
+# The fp32 split rule's two constants, both measured (tools/bench_linear_train.py, profiles/r14_linear_train.txt): ranges of at
 # least 16 row steps are 5-9 % ahead of 32-step ranges at 9600 rows (36 ranges against 18) and tie elsewhere; beyond ~256
 # ranges the reduction's traffic costs more than the shorter ranges save (32 x 4200 rows, N <= 128: 382-495 ranges 7-29 %
 # behind 255).  DFX_WGRAD_MIN_STEPS / DFX_WGRAD_MAX_RANGES are A/B aids.
 _WGRAD_MIN_STEPS = int(os.environ.get("DFX_WGRAD_MIN_STEPS", "16"))
 _WGRAD_MAX_RANGES = int(os.environ.get("DFX_WGRAD_MAX_RANGES", "256"))
 
+# The split rule's constants for the bf16 kernel, measured (tools/bench_linear_bf16_train.py --ranges, profiles/r22_linear_bf16_train.txt).
+# The kernel moves a range two to three times faster than the fp32 one, so the reduction's traffic weighs more and fewer, longer
+# ranges win: tiles x ranges within 512 workgroups (two per CU) and at most 64 ranges are within 5 % of the best count at every
+# shape tried (32 x 4200 rows: 256 -> 1024 177 us at 32 ranges against 193 at 48 and 213 at 64; 256 -> 256 90 us at 64, 87 at 96,
+# 111 at 191; 256 -> 64 64 us at 64, 61 at 96, 101 at 248).  The shortest range stays ``_WGRAD_MIN_STEPS`` = 16 steps, here of 32
+# rows: at 9600 and 4 x 4200 rows 16-step ranges are the best or within 2 % of it, 32-step ranges are 8-19 % behind.
+_WGRAD_BF16_SLOTS = 512
+_WGRAD_BF16_MAX_RANGES = 64
 
-def _wgrad_ranges(M, splits):
-    """(rows per range, ranges) the library makes of a request for ``splits`` ranges over M rows: whole 16-row steps, none empty."""
-    kper = ((M + splits - 1) // splits + 15) // 16 * 16
+
+def _wgrad_ranges(M, splits, step=16):
+    """(rows per range, ranges) the library makes of a request for ``splits`` ranges over M rows: whole steps of ``step`` rows
+    (16: the fp32 kernels, 32: ``dfx_gemm_bf16_wgrad``), none empty."""
+    kper = ((M + splits - 1) // splits + step - 1) // step * step
     return kper, (M + kper - 1) // kper
 
 
@@ -845,16 +855,45 @@ def _wgrad_tiles(N, K):
     return -(-N // 128) * -(-K // 128), 768
 
 
-def _wgrad_splits(M, N, K):
+def _wgrad_split_rule(M, N, K, step, slots, max_ranges):
     """Number of row ranges of the weight gradient dW[N,K] = dY[M,N]^T x[M,K] (pure host rule, ``_split_k``'s): the output has
-    only ``_wgrad_tiles`` tiles, so the M rows are cut into as many ranges as keep tiles x ranges within one resident round of
-    workgroups, each at least ``_WGRAD_MIN_STEPS`` 16-row steps long, at most ``_WGRAD_MAX_RANGES`` of them.  The result is
-    what the library will run: no range is empty."""
+    only ``_wgrad_tiles`` tiles, so the M rows are cut into as many ranges as keep tiles x ranges within ``slots`` workgroups,
+    each at least ``_WGRAD_MIN_STEPS`` steps of ``step`` rows long, at most ``max_ranges`` of them.  The result is what the
+    library will run: no range is empty."""
     if M <= 0:
         return 1
-    tiles, slots = _wgrad_tiles(N, K)
-    want = max(1, min(-(-M // 16) // _WGRAD_MIN_STEPS, slots // tiles, _WGRAD_MAX_RANGES, 65535))
-    return _wgrad_ranges(M, want)[1]
+    want = max(1, min(-(-M // step) // _WGRAD_MIN_STEPS, slots // _wgrad_tiles(N, K)[0], max_ranges, 65535))
+    return _wgrad_ranges(M, want, step)[1]
+
+
+def _wgrad_splits(M, N, K):
+    """The rule for ``dfx_gemm_wgrad_f32``: 16-row steps, one resident round of workgroups, ``_WGRAD_MAX_RANGES``."""
+    return _wgrad_split_rule(M, N, K, 16, _wgrad_tiles(N, K)[1], _WGRAD_MAX_RANGES)
+
+
+def _wgrad_bf16_ranges(M, splits):
+    return _wgrad_ranges(M, splits, 32)
+
+
+def _wgrad_bf16_splits(M, N, K):
+    """The rule for ``dfx_gemm_bf16_wgrad``: 32-row steps and the constants measured for it."""
+    return _wgrad_split_rule(M, N, K, 32, _WGRAD_BF16_SLOTS, _WGRAD_BF16_MAX_RANGES)
+
+
+def _linear_wgrad(what, entry, rule, go, x2, need_w, need_b, splits):
+    """-> (grad_w | None, grad_b | None) of go [M,N] and x2 [M,K] from one call of ``entry`` (``rule(M, N, K)`` row ranges, or
+    ``splits``); without a weight gradient no launch of it: a bias gradient on its own is ``go.sum(0)`` of the library."""
+    (M, N), K, dev = go.shape, x2.shape[1], x2.device
+    grad_w = grad_b = None
+    if need_w:
+        grad_w = torch.empty((N, K), dtype=torch.float32, device=dev)
+        grad_b = torch.empty((N,), dtype=torch.float32, device=dev) if need_b else None
+        n = rule(M, N, K) if splits is None else int(splits)
+        ws = torch.empty((n * (N * K + N),), dtype=torch.float32, device=dev) if n > 1 else None
+        _call(what + " (grad_w)", entry, dev, go.data_ptr(), N, x2.data_ptr(), K, grad_w.data_ptr(), K, _ptr(grad_b), M, N, K, n, _ptr(ws))
+    elif need_b:
+        grad_b = go.sum(0)
+    return grad_w, grad_b
 
 
 def linear_backward(grad_out, x, weight, need_x=True, need_w=True, need_b=True, splits=None):
@@ -873,27 +912,25 @@ def linear_backward(grad_out, x, weight, need_x=True, need_w=True, need_b=True, 
              "linear_backward is implemented for float32")
     _require(x2.shape[0] == M and N % 4 == 0 and K % 4 == 0, "linear_backward: grad_out [M,N], x [M,K] with N and K multiples of 4")
     dev = x.device
-    grad_x = grad_w = grad_b = None
+    grad_x = None
     if need_x:
         grad_x = torch.empty(x.shape, dtype=torch.float32, device=dev)
         for r0, r1 in _row_ranges(M, 4 * max(N, K)):
             _gemm_f32("linear_backward (grad_x)", dev, go.data_ptr() + r0 * N * 4, weight.data_ptr(), grad_x.data_ptr() + r0 * K * 4,
                       r1 - r0, K, N, N, K, K, b_is_kn=1)
-    if need_w:
-        grad_w = torch.empty((N, K), dtype=torch.float32, device=dev)
-        grad_b = torch.empty((N,), dtype=torch.float32, device=dev) if need_b else None
-        n = _wgrad_splits(M, N, K) if splits is None else int(splits)
-        ws = torch.empty((n * (N * K + N),), dtype=torch.float32, device=dev) if n > 1 else None
-        _call("linear_backward (grad_w)", "dfx_gemm_wgrad_f32", dev, go.data_ptr(), N, x2.data_ptr(), K, grad_w.data_ptr(), K,
-              _ptr(grad_b), M, N, K, n, _ptr(ws))
-    elif need_b:
-        grad_b = go.sum(0)
-    return grad_x, grad_w, grad_b
+    return (grad_x,) + _linear_wgrad("linear_backward", "dfx_gemm_wgrad_f32", _wgrad_splits, go, x2, need_w, need_b, splits)
 
 
 # The node's forward is the function above, bound here: what a module calls by name (``ops.linear``, ``ops.linear_train``) is
 # its route and can be wrapped or recorded as such; the product inside the autograd node is not a route of its own.
 _linear_forward = linear
+
+
+def _node_backward(backward, ctx, grad_output):
+    """the backward of both Linear nodes: (x, the weight operand) were saved; gradients for exactly the inputs that ask"""
+    x, weight = ctx.saved_tensors
+    need = ctx.needs_input_grad
+    return backward(grad_output.contiguous(), x, weight, need_x=need[0], need_w=need[1], need_b=need[2])
 
 
 class _LinearFunction(torch.autograd.Function):
@@ -907,10 +944,7 @@ class _LinearFunction(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_output):
-        x, weight = ctx.saved_tensors
-        need = ctx.needs_input_grad
-        # (looked up at call time: tests wrap it)
-        return linear_backward(grad_output.contiguous(), x, weight, need_x=need[0], need_w=need[1], need_b=need[2])
+        return _node_backward(linear_backward, ctx, grad_output)      # (looked up at call time: tests wrap it)
 
 
 def linear_train(x, weight, bias=None):
@@ -924,34 +958,6 @@ def linear_train(x, weight, bias=None):
 
 
 # ---- Linear in grad mode on bf16 products (include/dfx_gemm_bf16.h, dfx_gemm_bf16_wgrad; csrc/gemm_bf16_wgrad.hip) ----------------
-def _wgrad_bf16_ranges(M, splits):
-    """(rows per range, ranges) ``dfx_gemm_bf16_wgrad`` makes of a request for ``splits`` ranges over M rows: whole 32-row steps,
-    none empty."""
-    kper = ((M + splits - 1) // splits + 31) // 32 * 32
-    return kper, (M + kper - 1) // kper
-
-
-# The split rule's constants for this kernel, measured (tools/bench_linear_bf16_train.py --ranges, profiles/r22_linear_bf16_train.txt).
-# The kernel moves a range two to three times faster than the fp32 one, so the reduction's traffic weighs more and fewer, longer
-# ranges win: tiles x ranges within 512 workgroups (two per CU) and at most 64 ranges are within 5 % of the best count at every
-# shape tried (32 x 4200 rows: 256 -> 1024 177 us at 32 ranges against 193 at 48 and 213 at 64; 256 -> 256 90 us at 64, 87 at 96,
-# 111 at 191; 256 -> 64 64 us at 64, 61 at 96, 101 at 248).  The shortest range stays ``_WGRAD_MIN_STEPS`` = 16 steps, here of 32
-# rows: at 9600 and 4 x 4200 rows 16-step ranges are the best or within 2 % of it, 32-step ranges are 8-19 % behind.
-_WGRAD_BF16_SLOTS = 512
-_WGRAD_BF16_MAX_RANGES = 64
-
-
-def _wgrad_bf16_splits(M, N, K):
-    """Number of row ranges of the bf16 weight gradient: ``_wgrad_splits``' rule restated for this kernel's 32-row step, with
-    ``_wgrad_tiles``' tiles (128 x 128, or 64 x 128 for N <= 64) and the constants above.  The result is what the library will
-    run: no range is empty."""
-    if M <= 0:
-        return 1
-    tiles = _wgrad_tiles(N, K)[0]
-    want = max(1, min(-(-M // 32) // _WGRAD_MIN_STEPS, _WGRAD_BF16_SLOTS // tiles, _WGRAD_BF16_MAX_RANGES, 65535))
-    return _wgrad_bf16_ranges(M, want)[1]
-
-
 def linear_bf16_backward(grad_out, x, weight_t_bf16, need_x=True, need_w=True, need_b=True, splits=None):
     """Gradients of ``y = linear_bf16(x, weight_bf16, bias)`` on bf16 products with fp32 accumulation:
     -> (grad_x | None, grad_w | None, grad_b | None), fp32, fresh tensors.
@@ -970,23 +976,10 @@ def linear_bf16_backward(grad_out, x, weight_t_bf16, need_x=True, need_w=True, n
     _require(N % 8 == 0 and K % 8 == 0 and N > 0 and K > 0, "linear_bf16_backward: N and K must be multiples of 8")
     _require(grad_out.shape[-1] == N and x.shape[-1] == K, "linear_bf16_backward: grad_out [M,N], x [M,K], weight_t_bf16 [K,N]")
     go, x2 = grad_out.reshape(-1, N), x.reshape(-1, K)
-    M = go.shape[0]
-    _require(x2.shape[0] == M, "linear_bf16_backward: grad_out and x must have the same rows")
+    _require(x2.shape[0] == go.shape[0], "linear_bf16_backward: grad_out and x must have the same rows")
     _check_inputs([("grad_out", go), ("x", x2), ("weight_t_bf16", weight_t_bf16)])
-    dev = x.device
-    grad_x = grad_w = grad_b = None
-    if need_x:
-        grad_x = linear_bf16(go, weight_t_bf16).reshape(x.shape)
-    if need_w:
-        grad_w = torch.empty((N, K), dtype=torch.float32, device=dev)
-        grad_b = torch.empty((N,), dtype=torch.float32, device=dev) if need_b else None
-        n = _wgrad_bf16_splits(M, N, K) if splits is None else int(splits)
-        ws = torch.empty((n * (N * K + N),), dtype=torch.float32, device=dev) if n > 1 else None
-        _call("linear_bf16_backward (grad_w)", "dfx_gemm_bf16_wgrad", dev, go.data_ptr(), N, x2.data_ptr(), K, grad_w.data_ptr(), K,
-              _ptr(grad_b), M, N, K, n, _ptr(ws))
-    elif need_b:
-        grad_b = go.sum(0)
-    return grad_x, grad_w, grad_b
+    grad_x = linear_bf16(go, weight_t_bf16).reshape(x.shape) if need_x else None
+    return (grad_x,) + _linear_wgrad("linear_bf16_backward", "dfx_gemm_bf16_wgrad", _wgrad_bf16_splits, go, x2, need_w, need_b, splits)
 
 
 _linear_bf16_forward = linear_bf16      # (bound for the node, as ``_linear_forward`` is)
@@ -1004,11 +997,7 @@ class _LinearBf16Function(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_output):
-        x, weight_t_bf16 = ctx.saved_tensors
-        need = ctx.needs_input_grad
-        # (looked up at call time: tests wrap it)
-        gx, gw, gb = linear_bf16_backward(grad_output.contiguous(), x, weight_t_bf16, need_x=need[0], need_w=need[1], need_b=need[2])
-        return gx, gw, gb, None, None
+        return _node_backward(linear_bf16_backward, ctx, grad_output) + (None, None)      # (looked up at call time: tests wrap it)
 
 
 def linear_bf16_train(x, weight, bias, weight_bf16, weight_t_bf16):

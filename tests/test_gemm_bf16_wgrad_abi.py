@@ -1,6 +1,9 @@
-"""CPU, no launch: dfx_gemm_bf16_wgrad (include/dfx_gemm_bf16.h) is exported and bound, refuses what its header says it
-refuses before any launch; dfx.ops.linear_bf16_backward refuses CPU tensors, non-bf16 weight copies and N or K not multiples
-of 8; the LINEAR_BF16_TRAIN switch is off by default and the pair of bf16 weight copies follows its key."""
+"""CPU, no launch: the two weight-gradient entries on the one frame (csrc/wgrad_frame.h) - dfx_gemm_bf16_wgrad
+(include/dfx_gemm_bf16.h) and dfx_gemm_wgrad_f32 (include/dfx_gemm.h) - are exported and bound and refuse what their headers say
+they refuse before any launch, each with its own granule (8 or 4 columns) and its own bound on a range of rows;
+dfx.ops.linear_bf16_backward refuses CPU tensors, non-bf16 weight copies and N or K not multiples of 8; the LINEAR_BF16_TRAIN
+switch is off by default and the pair of bf16 weight copies follows its key."""
+import collections
 import os
 
 import pytest
@@ -15,15 +18,20 @@ EINVAL, ERANGE = -1, -3
 OK = (ONE, 16, ONE, 24, ONE, 24, ONE, 40, 16, 24, 1, TWO)
 DY, LDY, X, LDX, DW, LDW, DB, M, N, K, SPLITS, WS = range(12)
 
+# granule: columns N and K must be multiples of; step: rows of a K-step; reach: rows beyond a range that its 2 GiB bound allows for
+Entry = collections.namedtuple("Entry", "name granule step reach")
+BF16 = Entry("dfx_gemm_bf16_wgrad", 8, 32, 32)
+F32 = Entry("dfx_gemm_wgrad_f32", 4, 16, 0)
+
 
 def _lib_loaded():
     from dfx import _lib
     return _lib.load()
 
 
-def _refused(lib, args, cause, code):
-    rc = lib.dfx_gemm_bf16_wgrad(*args, None)
-    assert rc == code and cause in lib.dfx_last_error(), (args, rc, lib.dfx_last_error())
+def _refused(lib, e, args, cause, code):
+    rc = getattr(lib, e.name)(*args, None)
+    assert rc == code and cause in lib.dfx_last_error(), (e.name, args, rc, lib.dfx_last_error())
 
 
 def _swap(args, *pairs):
@@ -33,61 +41,120 @@ def _swap(args, *pairs):
     return tuple(args)
 
 
-def test_symbol_is_exported_and_bound():
+# ---- the checks of the frame, for either entry ---------------------------------------------------------------------------
+def symbol_is_exported_and_bound(e):
     from dfx import _lib
     lib = _lib_loaded()
-    assert hasattr(lib, "dfx_gemm_bf16_wgrad") and len(_lib.SIGNATURES["dfx_gemm_bf16_wgrad"]) == 13
-    assert lib.dfx_gemm_bf16_wgrad.argtypes == _lib.SIGNATURES["dfx_gemm_bf16_wgrad"]
+    assert hasattr(lib, e.name) and len(_lib.SIGNATURES[e.name]) == 13
+    assert getattr(lib, e.name).argtypes == _lib.SIGNATURES[e.name]
     assert lib.dfx_abi_version() == 5          # an addition: the version stays
 
 
-def test_bad_dimensions_and_pointers_are_refused():
+def bad_dimensions_and_pointers_are_refused(e):
     lib = _lib_loaded()
     for i, bad in ((M, -1), (N, -8), (K, -8), (SPLITS, 0), (SPLITS, -3)):
-        _refused(lib, _swap(OK, (i, bad)), b"bad dimension", EINVAL)
+        _refused(lib, e, _swap(OK, (i, bad)), b"bad dimension", EINVAL)
     for i in (DY, X, DW):
-        _refused(lib, _swap(OK, (i, 0)), b"null pointer", EINVAL)
-    _refused(lib, _swap(OK, (SPLITS, 2), (M, 100), (WS, 0)), b"needs a workspace", EINVAL)
+        _refused(lib, e, _swap(OK, (i, 0)), b"null pointer", EINVAL)
+    _refused(lib, e, _swap(OK, (SPLITS, 2), (M, 100), (WS, 0)), b"needs a workspace", EINVAL)
+
+
+def n_and_k_must_be_multiples_of_the_granule(e):
+    lib, g = _lib_loaded(), e.granule
+    cause = b"N and K must be multiples of %d" % g
+    for n in (g // 2, g + g // 2, 17, 256 + g // 2):          # (bf16: 4, 12, 17, 260)
+        _refused(lib, e, _swap(OK, (N, n), (LDY, 512)), cause, EINVAL)
+    for k in (g // 2, g + g // 2, 17, 256 + g // 2):
+        _refused(lib, e, _swap(OK, (K, k), (LDX, 512), (LDW, 512)), cause, EINVAL)
+
+
+def pitches_short_or_not_multiples_of_4_are_refused(e):
+    lib = _lib_loaded()
+    for i, short in ((LDY, 8), (LDX, 16), (LDW, 16)):
+        _refused(lib, e, _swap(OK, (i, short)), b"multiples of 4 that cover a row", EINVAL)
+    for i in (LDY, LDX, LDW):
+        for odd in (25, 26, 27):
+            _refused(lib, e, _swap(OK, (i, odd)), b"multiples of 4 that cover a row", EINVAL)
+
+
+def misalignment_is_refused(e):
+    lib = _lib_loaded()
+    for i in (DY, X, DW, WS):
+        _refused(lib, e, _swap(OK, (i, ODD)), b"16-byte aligned", EINVAL)
+
+
+def ranges_and_outputs_of_2_gib_are_refused(e):
+    lib = _lib_loaded()
+    rows = GIB2 // (24 * 4)                                                     # one range of X rows of 24 floats: 2 GiB
+    _refused(lib, e, _swap(OK, (M, rows + 32)), b"2 GiB", ERANGE)
+    _refused(lib, e, _swap(OK, (M, 4 * rows), (SPLITS, 2)), b"2 GiB", ERANGE)      # two ranges of 2 GiB each
+    _refused(lib, e, _swap(OK, (M, 64), (LDY, GIB2 // 4 // 64)), b"2 GiB", ERANGE)  # the pitch of dY alone
+    _refused(lib, e, _swap(OK, (LDW, GIB2 // 4 // 16)), b"2 GiB", ERANGE)          # dW
+    _refused(lib, e, _swap(OK, (M, e.step * 70000), (SPLITS, 70000)), b"too many splits", ERANGE)
+
+
+def the_range_bound_is_the_entrys_own(e):
+    """X rows of 32 floats: 2^24 rows are exactly 2 GiB.  Two ranges of `edge` = 2^24 - reach rows each are refused, two of one
+    step less pass the bound - shown without a launch by the next refusal in the entry's order, the missing workspace."""
+    lib = _lib_loaded()
+    rows = GIB2 // (32 * 4)
+    assert rows * 32 * 4 == GIB2 and rows % e.step == 0
+    edge = rows - e.reach
+    _refused(lib, e, _swap(OK, (LDX, 32), (M, 2 * edge), (SPLITS, 2), (WS, 0)), b"2 GiB", ERANGE)
+    _refused(lib, e, _swap(OK, (LDX, 32), (M, 2 * (edge - e.step)), (SPLITS, 2), (WS, 0)), b"needs a workspace", EINVAL)
+    _refused(lib, e, _swap(OK, (LDY, 32), (M, 2 * edge), (SPLITS, 2), (WS, 0)), b"2 GiB", ERANGE)     # the wider pitch counts, dY's too
+    _refused(lib, e, _swap(OK, (LDY, 32), (M, 2 * (edge - e.step)), (SPLITS, 2), (WS, 0)), b"needs a workspace", EINVAL)
+
+
+def empty_products_return_ok_without_a_launch(e):
+    fn = getattr(_lib_loaded(), e.name)
+    assert fn(*_swap(OK, (N, 0)), None) == 0
+    assert fn(*_swap(OK, (K, 0)), None) == 0
+    assert fn(0, 0, 0, 0, 0, 0, 0, 5, 0, 8, 1, 0, None) == 0       # asked before the pointers and pitches
+
+
+FRAME_CHECKS = [symbol_is_exported_and_bound, bad_dimensions_and_pointers_are_refused, n_and_k_must_be_multiples_of_the_granule,
+                pitches_short_or_not_multiples_of_4_are_refused, misalignment_is_refused, ranges_and_outputs_of_2_gib_are_refused,
+                the_range_bound_is_the_entrys_own, empty_products_return_ok_without_a_launch]
+
+
+# ---- dfx_gemm_wgrad_f32: every check of the frame ------------------------------------------------------------------------
+@pytest.mark.parametrize("check", FRAME_CHECKS, ids=lambda f: f.__name__)
+def test_fp32_entry(check):
+    check(F32)
+
+
+# ---- dfx_gemm_bf16_wgrad: the same checks under the names they have had --------------------------------------------------
+def test_symbol_is_exported_and_bound():
+    symbol_is_exported_and_bound(BF16)
+
+
+def test_bad_dimensions_and_pointers_are_refused():
+    bad_dimensions_and_pointers_are_refused(BF16)
 
 
 def test_n_and_k_must_be_multiples_of_8():
-    lib = _lib_loaded()
-    for n in (4, 12, 17, 260):
-        _refused(lib, _swap(OK, (N, n), (LDY, 512)), b"multiples of 8", EINVAL)
-    for k in (4, 12, 17, 260):
-        _refused(lib, _swap(OK, (K, k), (LDX, 512), (LDW, 512)), b"multiples of 8", EINVAL)
+    n_and_k_must_be_multiples_of_the_granule(BF16)
 
 
 def test_pitches_short_or_not_multiples_of_4_are_refused():
-    lib = _lib_loaded()
-    for i, short in ((LDY, 8), (LDX, 16), (LDW, 16)):
-        _refused(lib, _swap(OK, (i, short)), b"multiples of 4 that cover a row", EINVAL)
-    for i in (LDY, LDX, LDW):
-        for odd in (25, 26, 27):
-            _refused(lib, _swap(OK, (i, odd)), b"multiples of 4 that cover a row", EINVAL)
+    pitches_short_or_not_multiples_of_4_are_refused(BF16)
 
 
 def test_misalignment_is_refused():
-    lib = _lib_loaded()
-    for i in (DY, X, DW, WS):
-        _refused(lib, _swap(OK, (i, ODD)), b"16-byte aligned", EINVAL)
+    misalignment_is_refused(BF16)
 
 
 def test_ranges_and_outputs_of_2_gib_are_refused():
-    lib = _lib_loaded()
-    rows = GIB2 // (24 * 4)                                                     # one range of X rows of 24 floats: 2 GiB
-    _refused(lib, _swap(OK, (M, rows + 32)), b"2 GiB", ERANGE)
-    _refused(lib, _swap(OK, (M, 4 * rows), (SPLITS, 2)), b"2 GiB", ERANGE)      # two ranges of 2 GiB each
-    _refused(lib, _swap(OK, (M, 64), (LDY, GIB2 // 4 // 64)), b"2 GiB", ERANGE)  # the pitch of dY alone
-    _refused(lib, _swap(OK, (LDW, GIB2 // 4 // 16)), b"2 GiB", ERANGE)          # dW
-    _refused(lib, _swap(OK, (M, 32 * 70000), (SPLITS, 70000)), b"too many splits", ERANGE)
+    ranges_and_outputs_of_2_gib_are_refused(BF16)
+
+
+def test_the_range_bound_reaches_one_step_further():
+    the_range_bound_is_the_entrys_own(BF16)
 
 
 def test_empty_products_return_ok_without_a_launch():
-    lib = _lib_loaded()
-    assert lib.dfx_gemm_bf16_wgrad(*_swap(OK, (N, 0)), None) == 0
-    assert lib.dfx_gemm_bf16_wgrad(*_swap(OK, (K, 0)), None) == 0
-    assert lib.dfx_gemm_bf16_wgrad(0, 0, 0, 0, 0, 0, 0, 5, 0, 8, 1, 0, None) == 0       # asked before the pointers and pitches
+    empty_products_return_ok_without_a_launch(BF16)
 
 
 def test_linear_bf16_backward_refuses_cpu_tensors_other_copies_and_sizes_not_multiples_of_8():

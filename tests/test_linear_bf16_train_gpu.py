@@ -1,6 +1,8 @@
-"""GPU: the bf16 weight-gradient kernel (csrc/gemm_bf16_wgrad.hip, dfx_gemm_bf16_wgrad) and dfx.ops.linear_bf16_backward - exact
-cases bit for bit at every element, the rounding of both operands, random operands against fp64 with a worked-out bound on every
-element, padding, run-to-run bits, the need_* flags and row pitches.
+"""GPU: the bf16 weight-gradient kernel (csrc/gemm_bf16_wgrad.hip on csrc/wgrad_frame.h, dfx_gemm_bf16_wgrad) and
+dfx.ops.linear_bf16_backward - exact cases bit for bit at every element, the rounding of both operands, random operands against
+fp64 with a worked-out bound on every element, padding, run-to-run bits, the need_* flags and row pitches.  What tests the
+frame and not the operand path - exact integers, row pitches, tails - runs on the fp32 entry too (csrc/gemm_wgrad.hip,
+dfx_gemm_wgrad_f32, dfx.ops.linear_backward).
 
 Bounds (u = 2^-8, the unit roundoff of bf16; products of bf16 operands are exact in fp32):
   dW vs fp64 of the ROUNDED operands:   |dW - ref| <= M 2^-23 S + 2^-23 |ref|,  S = |bf16(dY)|^T |bf16(X)|
@@ -9,7 +11,9 @@ Bounds (u = 2^-8, the unit roundoff of bf16; products of bf16 operands are exact
   db (from the unrounded dY):           |db - ref| <= M 2^-23 sum_m |dY|
   grad_x = bf16(dY) @ W:                |gx - ref| <= N 2^-23 S' + 2^-23 |ref|,  S' = |bf16(dY)| |W|   (tests/test_gemm_bf16_gpu.py's
       bound with K -> N)
+  fp32 entry, dW vs fp64 of the operands: |dW - ref| <= M 2^-23 S + 2^-23 |ref|,  S = |dY|^T |X|   (no rounding of the operands)
 Every case prints its worst ratio to the bound (pytest -s shows them)."""
+import collections
 import functools
 
 import pytest
@@ -21,6 +25,9 @@ pytestmark = pytest.mark.gpu
 # the 64-row tile (N <= 64)
 SHAPES = [(1, 8, 8, 1), (15, 24, 40, 1), (17, 8, 264, 1), (33, 136, 264, 1), (100, 256, 256, 2), (1000, 1024, 256, 7),
           (1000, 256, 1024, 7), (1000, 64, 72, 3)]
+# the fp32 entry takes every multiple of 4: one quad, a quad past a column tile, one quad past a 128 tile in both directions, the
+# 64-row tile with a ragged last range
+SHAPES_F32 = SHAPES + [(1, 4, 4, 1), (17, 12, 260, 1), (33, 132, 260, 1), (1000, 60, 68, 3)]
 U = 2.0 ** -8
 EPS = 2.0 ** -23
 ids = lambda s: "x".join(map(str, s))      # noqa: E731
@@ -31,6 +38,10 @@ def _gen(shape, salt):
     return torch.Generator(device="cuda").manual_seed(1000003 * M + 1009 * N + K + salt)
 
 
+# an entry of the frame: its symbol, and the (dW, db) half of its backward function on contiguous operands
+Entry = collections.namedtuple("Entry", "name wgrad")
+
+
 def _wgrad(go, x, splits, need_b=True):
     from dfx import ops
     N = go.shape[1]
@@ -39,14 +50,25 @@ def _wgrad(go, x, splits, need_b=True):
     return gw, gb
 
 
-def _raw(buf_y, ldy, buf_x, ldx, M, N, K, splits, ldw=None, with_db=True):
+def _wgrad_f32(go, x, splits, need_b=True):
+    from dfx import ops
+    w = torch.zeros(go.shape[1], x.shape[1], device="cuda")
+    _, gw, gb = ops.linear_backward(go, x, w, need_x=False, need_w=True, need_b=need_b, splits=splits)
+    return gw, gb
+
+
+BF16 = Entry("dfx_gemm_bf16_wgrad", _wgrad)
+F32 = Entry("dfx_gemm_wgrad_f32", _wgrad_f32)
+
+
+def _raw(buf_y, ldy, buf_x, ldx, M, N, K, splits, ldw=None, with_db=True, entry=BF16):
     """the entry point itself, on operands with row pitches of their own"""
     from dfx import ops
     ldw = K if ldw is None else ldw
     dW = torch.full((N, ldw), float("nan"), device="cuda")
     db = torch.full((N,), float("nan"), device="cuda") if with_db else None
     ws = torch.full((splits * (N * K + N),), float("nan"), device="cuda") if splits > 1 else None
-    ops._call("test", "dfx_gemm_bf16_wgrad", buf_y.device, buf_y.data_ptr(), ldy, buf_x.data_ptr(), ldx, dW.data_ptr(), ldw,
+    ops._call("test", entry.name, buf_y.device, buf_y.data_ptr(), ldy, buf_x.data_ptr(), ldx, dW.data_ptr(), ldw,
               ops._ptr(db), M, N, K, splits, ops._ptr(ws))
     return dW, db
 
@@ -58,19 +80,29 @@ def _worst(err, bound, what):
 
 
 # ---- 1. exact ----------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("shape", SHAPES, ids=ids)
-def test_integer_operands_are_bit_equal_at_every_element(shape):
-    """integers in [-8, 8] are bf16 numbers and every partial sum stays below 2^24: fp32 is exact in any order"""
+def _integer_operands_are_bit_equal(entry, shape):
     M, N, K, splits = shape
     g = _gen(shape, 1)
     go = torch.randint(-8, 9, (M, N), generator=g, device="cuda").float()
     x = torch.randint(-8, 9, (M, K), generator=g, device="cuda").float()
-    gw, gb = _wgrad(go, x, splits)
+    gw, gb = entry.wgrad(go, x, splits)
     ref_w, ref_b = go.double().t() @ x.double(), go.double().sum(0)
     assert gw.shape == (N, K) and gb.shape == (N,) and gw.dtype == gb.dtype == torch.float32
     bad = (gw.double() != ref_w).nonzero()
     assert bad.numel() == 0, (bad[:8].tolist(), len(bad))
     assert torch.equal(gb.double(), ref_b)
+
+
+@pytest.mark.parametrize("shape", SHAPES, ids=ids)
+def test_integer_operands_are_bit_equal_at_every_element(shape):
+    """integers in [-8, 8] are bf16 numbers and every partial sum stays below 2^24: fp32 is exact in any order"""
+    _integer_operands_are_bit_equal(BF16, shape)
+
+
+@pytest.mark.parametrize("shape", SHAPES_F32, ids=ids)
+def test_fp32_integer_operands_are_bit_equal_at_every_element(shape):
+    """products of at most 64 over at most 1000 rows: every partial sum stays below 64 000 < 2^24, fp32 is exact in any order"""
+    _integer_operands_are_bit_equal(F32, shape)
 
 
 def test_no_rows_write_zeros():
@@ -150,20 +182,30 @@ def test_random_operands_meet_the_bounds_at_every_element(shape):
 
 
 # ---- 4. padding --------------------------------------------------------------------------------------------------------
-def test_tail_rows_and_columns_are_exactly_zero():
-    """M = 33, N = 64, K = 40, operands of order 1024 inside larger buffers of the same order: rows beyond M, the columns between
-    N / K and the pitch, and the padded part of the tile may only ever be read as zeros - one stray product is ~10^6 against a
-    bound of ~10^2"""
+def _tail_rows_and_columns_read_as_zeros(entry, rounded):
+    """``rounded``: what the entry makes of an operand before the products (bf16: the rounding; fp32: nothing)"""
     M, N, K, ldy, ldx = 33, 64, 40, 72, 52
     g = torch.Generator(device="cuda").manual_seed(33)
     by = (torch.rand(M + 40, ldy, generator=g, device="cuda") + 0.5) * 1024
     bx = (torch.rand(M + 40, ldx, generator=g, device="cuda") + 0.5) * 1024
     go, x = by[:M, :N], bx[:M, :K]
-    gw, gb = _raw(by, ldy, bx, ldx, M, N, K, 1)
-    gr, xr = go.to(torch.bfloat16).double(), x.to(torch.bfloat16).double()
+    gw, gb = _raw(by, ldy, bx, ldx, M, N, K, 1, entry=entry)
+    gr, xr = rounded(go).double(), rounded(x).double()
     ref = gr.t() @ xr
-    assert _worst((gw.double() - ref).abs(), M * EPS * (gr.abs().t() @ xr.abs()) + EPS * ref.abs(), "padding dW") <= 1
-    assert _worst((gb.double() - go.double().sum(0)).abs(), M * EPS * go.double().abs().sum(0), "padding db") <= 1
+    assert _worst((gw.double() - ref).abs(), M * EPS * (gr.abs().t() @ xr.abs()) + EPS * ref.abs(), f"{entry.name} padding dW") <= 1
+    assert _worst((gb.double() - go.double().sum(0)).abs(), M * EPS * go.double().abs().sum(0), f"{entry.name} padding db") <= 1
+
+
+def test_tail_rows_and_columns_are_exactly_zero():
+    """M = 33, N = 64, K = 40, operands of order 1024 inside larger buffers of the same order: rows beyond M, the columns between
+    N / K and the pitch, and the padded part of the tile may only ever be read as zeros - one stray product is ~10^6 against a
+    bound of ~10^2"""
+    _tail_rows_and_columns_read_as_zeros(BF16, lambda t: t.to(torch.bfloat16))
+
+
+def test_fp32_tail_rows_and_columns_are_exactly_zero():
+    """the same buffers through the fp32 entry, against fp64 of the unrounded operands"""
+    _tail_rows_and_columns_read_as_zeros(F32, lambda t: t)
 
 
 # ---- 5. the same bits --------------------------------------------------------------------------------------------------
@@ -199,17 +241,29 @@ def test_unrequested_gradients_are_none_and_the_others_keep_their_bits():
             assert torch.equal(got[2], go.sum(0))
 
 
-@pytest.mark.parametrize("shape", [(33, 136, 264, 1), (100, 256, 256, 2), (1000, 64, 72, 3)], ids=ids)
-def test_row_pitches_give_the_bits_of_the_packed_call(shape):
+PITCHED = [(33, 136, 264, 1), (100, 256, 256, 2), (1000, 64, 72, 3)]
+
+
+def _row_pitches_give_the_bits_of_the_packed_call(entry, shape):
     M, N, K, splits = shape
     go, x, _, _ = _randoms(shape)
-    gw, gb = _wgrad(go, x, splits)
+    gw, gb = entry.wgrad(go, x, splits)
     ldy, ldx, ldw = N + 12, K + 4, K + 8
     by = torch.full((M, ldy), 1e6, device="cuda")
     bx = torch.full((M, ldx), -1e6, device="cuda")
     by[:, :N], bx[:, :K] = go, x
-    pw, pb = _raw(by, ldy, bx, ldx, M, N, K, splits, ldw=ldw)
+    pw, pb = _raw(by, ldy, bx, ldx, M, N, K, splits, ldw=ldw, entry=entry)
     assert torch.equal(pw[:, :K], gw) and torch.equal(pb, gb)
     assert torch.isnan(pw[:, K:]).all()                        # nothing outside [N, K] of dW is written
-    nw, nb = _raw(by, ldy, bx, ldx, M, N, K, splits, with_db=False)
+    nw, nb = _raw(by, ldy, bx, ldx, M, N, K, splits, with_db=False, entry=entry)
     assert nb is None and torch.equal(nw, gw)
+
+
+@pytest.mark.parametrize("shape", PITCHED, ids=ids)
+def test_row_pitches_give_the_bits_of_the_packed_call(shape):
+    _row_pitches_give_the_bits_of_the_packed_call(BF16, shape)
+
+
+@pytest.mark.parametrize("shape", PITCHED + [(33, 132, 260, 1)], ids=ids)
+def test_fp32_row_pitches_give_the_bits_of_the_packed_call(shape):
+    _row_pitches_give_the_bits_of_the_packed_call(F32, shape)
